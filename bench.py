@@ -13,7 +13,8 @@ A step = x.clone -> forward -> L1 loss -> backward -> (N>1: RCCL gradient all-re
 Prints ONE JSON line on rank 0.
 
 Order inside a rank: build -> W warm-up steps -> barrier + synchronize -> K timed steps (nothing but the step and one
-HIP event per step boundary on the launch stream) -> synchronize + barrier -> [rank 0, N=1: CPU oracle leg] ->
+HIP event per step boundary on the launch stream) -> synchronize + barrier -> [rank 0, --dump-outputs DIR: the last
+timed step's loss, forward outputs, updated parameters and gradients to DIR/*.npy] -> [rank 0, N=1: CPU oracle leg] ->
 a separate, untimed pass with HIP events around every matrix-core launch (the roofline families).  `value` is
 patches / wall-clock of the K timed steps (max over ranks); `step_ms` gives median / min / max of the K steps.
 """
@@ -102,6 +103,50 @@ def cpu_baseline(size, state_dict, x, tgt, timed=3):
     return rec, first
 
 
+DUMP_BUDGET_ELEMS = 15 << 20     # --dump-outputs: 60 MB of float32 in all, under the 64 MB cap with the .npy headers
+
+
+def _named_tensors(obj, name):
+    """(name, tensor) for every tensor of a forward's return value (tensor / tuple / list / dict, nested)."""
+    if torch.is_tensor(obj):
+        yield name, obj
+    elif isinstance(obj, (list, tuple)):
+        for i, o in enumerate(obj):
+            yield from _named_tensors(o, f"{name}_{i}")
+    elif isinstance(obj, dict):
+        for k, o in obj.items():
+            yield from _named_tensors(o, f"{name}_{k}")
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` ({name: device tensor}) as out_dir/<name>.npy in float32.  Arrays that fit the shared budget
+    are written whole; the budget left over is split evenly among the larger ones (equal sizes, equal shares), each of
+    which is written as a fixed sample: sorted distinct flat indices drawn from a generator seeded by the array's size
+    and share.  So two runs (or two builds) with the same arguments pick the same elements, and arrays of one size
+    (params / grads) are sampled at the same indices.  Returns {name: {shape, saved, sampled}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    caps, left, prev = {}, DUMP_BUDGET_ELEMS, None
+    by_size = sorted(arrays, key=lambda n: arrays[n].numel())
+    for i, n in enumerate(by_size):                 # smallest first: each takes min(its size, an even share of the rest)
+        size = arrays[n].numel()
+        caps[n] = caps[prev] if prev is not None and arrays[prev].numel() == size else min(size, left // (len(by_size) - i))
+        left -= caps[n]
+        prev = n
+    info = {}
+    for n, t in arrays.items():
+        a = t.detach()
+        sampled = caps[n] < a.numel()
+        if sampled:
+            rng = np.random.default_rng([a.numel(), caps[n]])
+            idx = np.sort(rng.choice(a.numel(), caps[n], replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        a = a.float().cpu().numpy()
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+        info[n] = {"shape": list(t.shape), "saved": int(a.size), "sampled": sampled}
+    return info
+
+
 def self_launch(n):
     """`python bench.py --gpus N` started plainly: start the N ranks as ONE child job of torch.distributed.run with
     the flags this process got, from a parent that has made no GPU call (importing torch makes none).  Rank 0's JSON
@@ -147,7 +192,16 @@ def main():
                     help="steps of the separate per-kernel timing pass (0: max(--steps, 50), at most 100)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo + --workload stub: the launch / exchange / report plumbing on CPU ranks (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0, after the timed steps: what the LAST timed step computed -- loss, the trained network's "
+                         "forward outputs (output*), its updated parameters and their gradients (params / grads, flat "
+                         "in named_parameters order, zeros for a parameter without gradient, sampled at the same "
+                         "indices) -- as DIR/<name>.npy, float32, at most 64 MB in all (larger arrays "
+                         "as a fixed seeded sample).  Inputs and initial weights are seeded: same arguments, same inputs, "
+                         "and the flavr step is bit-reproducible, so two runs write identical files")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ   # one rank of a torch.distributed.run job
     if args.gpus > 1 and not launched:
@@ -347,10 +401,18 @@ def main():
     gc_log = []
     gc_cb = lambda phase, info: gc_log.append((info["generation"], time.perf_counter())) if phase == "stop" else None
     gc.callbacks.append(gc_cb)
+    # --dump-outputs: a forward hook on the trained network (cfg4: the student), present in every timed step so that
+    # all of them take the same path; it keeps the forward's return value of the last one only
+    net = student if args.workload == "cfg4" else model
+    fwd_out, keep = [], [False]
+    hook_at = args.steps - 1 if args.dump_outputs and rank == 0 else -1
+    if hook_at >= 0:
+        hook = net.register_forward_hook(lambda mod, inp, out: fwd_out.append(out) if keep[0] else None)
     t0 = time.perf_counter()
     if marks:
         marks[0].record()
     for i in range(args.steps):
+        keep[0] = i == hook_at
         loss = step()
         if marks:
             marks[i + 1].record()
@@ -359,6 +421,20 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     gc.callbacks.remove(gc_cb)
+    dumped = None
+    if hook_at >= 0:    # now, before the CPU leg reloads the initial weights and the per-kernel pass trains on
+        hook.remove()
+        arrays = {"loss": loss.reshape(1)}
+        arrays.update(_named_tensors(fwd_out[-1], "output"))
+        named = list(model.named_parameters())
+        arrays["params"] = torch.cat([p.detach().reshape(-1) for _, p in named])
+        # zeros where a parameter got no gradient, so that params and grads line up element for element
+        arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                     for _, p in named])
+        dumped = {"arrays": dump_outputs(args.dump_outputs, arrays),
+                  "params_without_grad": [n for n, p in named if p.grad is None]}
+        del arrays
+        fwd_out.clear()
     if dist.is_initialized():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -482,6 +558,8 @@ def main():
         if cpu_rec is not None:
             rec["cpu_baseline"] = cpu_rec
             rec["parity_vs_cpu"] = parity
+        if dumped is not None:
+            rec["dump_outputs"] = dict({"dir": args.dump_outputs}, **dumped)
         print(json.dumps(rec), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

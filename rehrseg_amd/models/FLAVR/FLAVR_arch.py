@@ -136,7 +136,7 @@ class UNet_3D_3D(nn.Module):
         pad_rows = (-co) % 32
         w = F.pad(c.weight, (0, 0, 0, 0, 0, 0, 0, pad_rows)).unsqueeze(2)
         b = F.pad(c.bias, (0, pad_rows))
-        x = F.pad(fused[:, :, 0], (3, 3, 3, 3), mode="reflect").unsqueeze(2)
+        x = ops.reflect_pad_hw(fused[:, :, 0], 3).unsqueeze(2)
         return ops.fused_conv3d(x, w, b, 1, 0)[:, :co, 0]
 
     def forward(self, images, return_inetermediate_uncertainty=False, return_inetermediate_feature=False):

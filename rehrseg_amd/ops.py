@@ -724,6 +724,34 @@ def upsample_depth(x, scale):
     return _UpsampleDepth.apply(x, Do)
 
 
+def _reflect_fold(g, dim, p):
+    """Adjoint of reflection padding by p along `dim`: the interior plus the p mirrored border slices, added in a fixed
+    order (the input element i receives padded elements p+i and, near an edge, its mirror)."""
+    n = g.shape[dim] - 2 * p
+    out = g.narrow(dim, p, n).clone()
+    out.narrow(dim, 1, p).add_(g.narrow(dim, 0, p).flip(dim))
+    out.narrow(dim, n - 1 - p, p).add_(g.narrow(dim, n + p, p).flip(dim))
+    return out
+
+
+class _ReflectPadHW(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p):
+        ctx.p = p
+        return torch.nn.functional.pad(x, (p, p, p, p), mode="reflect")
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _reflect_fold(_reflect_fold(dy, dy.dim() - 1, ctx.p), dy.dim() - 2, ctx.p), None
+
+
+def reflect_pad_hw(x, p):
+    """F.pad(x, (p, p, p, p), mode="reflect") on the last two dims with a run-to-run reproducible backward: ATen's
+    reflection-pad backward accumulates the border gradients with float atomics, whose order varies between runs, and
+    over optimizer steps those last-bit differences grow (Reproducibility)."""
+    return _ReflectPadHW.apply(x, int(p))
+
+
 class _UasrMix(torch.autograd.Function):
     """Softmax blend of the K candidate pairs + uncertainty of the UASR head -- see rehr_uasr_mix_fwd_f32."""
 

@@ -49,7 +49,7 @@ def test_integration_snippet_in_clean_interpreter(tmp_path):
     assert r.returncode == 0 and "DROPIN_OK" in r.stdout, r.stderr[-2000:]
 
 
-def test_reference_data_imports_resolve():
+def test_reference_data_imports_resolve(tmp_path):
     """train_all.py:24,28 name the data set classes and blur helpers by these paths."""
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from utils.train_set import TrainSetMultiple, TrainSetMultipleSegSREfficient\n"
@@ -64,7 +64,7 @@ def test_reference_data_imports_resolve():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, "-c", code % os.path.join(root, "rehrseg_amd")], capture_output=True, text=True,
-                         cwd="/tmp", env={k: v for k, v in os.environ.items() if k != "PYTHONPATH"})
+                         cwd=str(tmp_path), env={k: v for k, v in os.environ.items() if k != "PYTHONPATH"})
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 

@@ -41,3 +41,29 @@ def test_flavr_gpu_vs_oracle_batch_and_odd_extent():
             continue
         n = float(osd[k].grad.norm())
         assert float((p.grad.cpu() - osd[k].grad).norm()) <= 1e-3 * n + 1e-9, k
+
+
+def test_flavr_step_is_bit_reproducible():
+    """bench.py's flavr step, forward + backward from the same weights, twice in one process: output and every
+    gradient bit-equal (the reflection pad of the tail has a fixed-order backward, ops.reflect_pad_hw)."""
+    from oracle.detinit import det_input, det_tensor
+    from rehrseg_amd.models.FLAVR.FLAVR_arch import UNet_3D_3D
+    from rehrseg_amd.parallel import PatchParallel
+    m = UNet_3D_3D(1, "unet_18", 32, 4)
+    m.load_state_dict({k: det_tensor(k, tuple(v.shape)) for k, v in m.state_dict().items()})
+    m = m.cuda()
+    pp = PatchParallel(m)
+    x = det_input("repro.x", (1, 1, 32, 128, 128), "rand").cuda()
+    tgt = det_input("repro.t", (1, 1, 4, 128, 128), "rand").cuda()
+    runs = []
+    for _ in range(2):
+        pp.zero_grad()
+        out = m(x.clone())
+        (out - tgt).abs().mean().backward()
+        pp.reduce_gradients()
+        torch.cuda.synchronize()
+        runs.append((out.detach().clone(), {n: p.grad.detach().clone() for n, p in m.named_parameters()
+                                             if p.grad is not None}))
+    assert torch.equal(runs[0][0], runs[1][0])
+    differ = [n for n in runs[0][1] if not torch.equal(runs[0][1][n], runs[1][1][n])]
+    assert not differ, differ

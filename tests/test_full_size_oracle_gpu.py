@@ -16,6 +16,11 @@ One oracle step takes ~30 s in fp32; the fp64 legs take 110 s (cfg-2) and 350 s 
 box's 128 host threads, so by default the yardstick is read from tests/golden/conditioning_cfg{2,3}.json -- the
 fp32-vs-fp64 distances this very test measured there (same deterministic inputs and weights; REHR_PARITY_FP64=1
 recomputes them live and is how the fixtures and profiles/r02_parity_cfg*.json were produced).
+A recorded distance only describes the fp32 run it was measured on, and the fp32 backward's cancelling bias gradients
+(a sum over every voxel) change with the host's threads: encoder.layer1.0.conv2.0.bias sits 2.8e-4 from fp64 on the
+host that recorded conditioning_cfg2.json and 1.0e-3 on a 16-thread host.  So for cfg-2's small tensors the oracle's
+fp64 gradients are stored (tests/golden/fp64_small_grads_cfg2.npz, tools/gen_golden_fp64_small_grads.py) and their
+distance is measured live, against the fp32 run this test just made, as REHR_PARITY_FP64=1 does for every tensor.
 """
 import json
 import os
@@ -36,6 +41,13 @@ def _dtypes():
 
 def _conditioning(tag):
     return json.load(open(os.path.join(ROOT, "tests", "golden", f"conditioning_{tag}.json")))
+
+
+def _stored_fp64_grads(tag):
+    """The oracle's fp64 gradients of the tensors tools/gen_golden_fp64_small_grads.py stored for `tag`."""
+    import numpy as np
+    g = np.load(os.path.join(ROOT, "tests", "golden", f"fp64_small_grads_{tag}.npz"))
+    return {k: torch.from_numpy(g[k]) for k in g.files if not k.startswith("__")}
 
 
 class heartbeat:
@@ -67,7 +79,8 @@ def _l2rel(a, b):
 
 
 def _gradient_table(hip_grads, g32, g64, skip=(), cond=None):
-    """g64: the oracle's fp64 gradients (live run) or None, in which case `cond` holds the recorded distances."""
+    """g64: the oracle's fp64 gradients (live run, or stored ones for some tensors) or None; `cond` holds the recorded
+    distances of the tensors g64 lacks."""
     rows, bad = [], []
     for k, ref in g32.items():
         if k in skip or ref is None:
@@ -76,7 +89,7 @@ def _gradient_table(hip_grads, g32, g64, skip=(), cond=None):
         if n == 0.0:
             continue
         d_hip = _l2rel(hip_grads[k].cpu(), ref)
-        if g64 is not None:
+        if g64 is not None and k in g64:
             d_cond = _l2rel(ref, g64[k])          # the reference path's own fp32 rounding distance
             d_hip64 = _l2rel(hip_grads[k].cpu(), g64[k])
         else:
@@ -90,9 +103,10 @@ def _gradient_table(hip_grads, g32, g64, skip=(), cond=None):
 def _report(tag, summary, rows):
     over = [r for r in rows if r["hip_vs_cpu_fp32"] > 1e-3]
     worst = max(rows, key=lambda r: r["hip_vs_cpu_fp32"])
+    h64 = [r["hip_vs_cpu_fp64"] for r in rows if r["hip_vs_cpu_fp64"] is not None]
     summary.update(n_gradients=len(rows), n_over_1e3=len(over), worst=worst,
                    median_hip_vs_cpu_fp32=sorted(r["hip_vs_cpu_fp32"] for r in rows)[len(rows) // 2],
-                   max_hip_vs_cpu_fp64=(max(r["hip_vs_cpu_fp64"] for r in rows) if rows[0]["hip_vs_cpu_fp64"] is not None else None),
+                   max_hip_vs_cpu_fp64=max(h64) if h64 else None,
                    max_cpu_fp32_vs_fp64=max(r["cpu_fp32_vs_fp64"] for r in rows))
     print(f"[{tag}] " + json.dumps(summary))
     for r in sorted(rows, key=lambda r: -r["hip_vs_cpu_fp32"])[:12]:
@@ -143,8 +157,10 @@ def test_cfg2_flavr_128cube_against_cpu_reference_path():
                                                runs[torch.float64][0].abs().max())}
     else:
         cj = _conditioning("cfg2")
-        rows, bad = _gradient_table(hip, g32, None, cond=cj["cpu_fp32_vs_fp64"])
-        extra = {"loss_cpu_fp64": cj["loss_cpu_fp64"], "yardstick": "tests/golden/conditioning_cfg2.json"}
+        rows, bad = _gradient_table(hip, g32, _stored_fp64_grads("cfg2"), cond=cj["cpu_fp32_vs_fp64"])
+        extra = {"loss_cpu_fp64": cj["loss_cpu_fp64"],
+                 "yardstick": "tests/golden/conditioning_cfg2.json; small tensors live against "
+                              "tests/golden/fp64_small_grads_cfg2.npz"}
     _report("cfg2", dict({"fwd_max_rel": fwd, "loss_hip": float(loss), "loss_cpu_fp32": l32}, **extra), rows)
     assert fwd <= 1e-3
     assert abs(float(loss) - l32) <= 1e-4 * abs(l32)

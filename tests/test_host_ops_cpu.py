@@ -272,3 +272,16 @@ def test_uasr_mix(emu, K, D, hw):
     for a, e in zip(got, ref):
         _cmp(a, e, 1e-6)
     assert not ops.uasr_mix_supported(om, ue[:, :-1], D)
+
+
+@pytest.mark.parametrize("shape,p", [((2, 5, 9, 11), 3), ((1, 3, 5, 4), 3), ((1, 2, 4, 6), 1)])
+def test_reflect_pad_hw_equals_torch_reflect_pad(shape, p):
+    """The FLAVR tail's reflection pad: same forward as F.pad(mode="reflect"), backward the same adjoint (in a fixed
+    summation order instead of ATen's atomics)."""
+    x = _rand(*shape).requires_grad_()
+    ref = F.pad(x, (p, p, p, p), mode="reflect")
+    got = ops.reflect_pad_hw(x, p)
+    assert torch.equal(got, ref)
+    g = torch.randn_like(ref)
+    _cmp(torch.autograd.grad(got, x, g)[0], torch.autograd.grad(ref, x, g)[0])
+    assert torch.autograd.gradcheck(lambda t: ops.reflect_pad_hw(t, p), (x,))

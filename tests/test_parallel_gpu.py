@@ -1,5 +1,7 @@
 """PatchParallel on the device (single rank): the weight-gradient kernels write straight into the flat gradient
 buffer; the result must equal plain autograd accumulation, also over two accumulated backward passes."""
+import socket
+
 import pytest
 import torch
 
@@ -8,6 +10,12 @@ from rehrseg_amd.models.FLAVR.FLAVR_arch import UNet_3D_3D
 from rehrseg_amd.parallel import PatchParallel
 
 pytestmark = pytest.mark.gpu
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
 
 
 def _model(dev):
@@ -54,7 +62,6 @@ OVERLAP_SCRIPT = r"""
 import json, os, sys
 sys.path.insert(0, {root!r})
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-os.environ.setdefault("MASTER_PORT", "29533")
 import torch
 import torch.distributed as dist
 torch.cuda.set_device(0)
@@ -106,7 +113,7 @@ def test_hook_launched_buckets_with_direct_writes_under_rccl_world1(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
     r = subprocess.run([sys.executable, "-c", OVERLAP_SCRIPT.format(root=root)], cwd=str(tmp_path), env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -177,7 +184,7 @@ def test_two_ranks_exchange_on_the_device(tmp_path):
     script.write_text(TWO_RANK_SCRIPT.format(root=root))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", "29547", str(script)], cwd=str(tmp_path), env=env,
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(script)], cwd=str(tmp_path), env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
