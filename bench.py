@@ -14,9 +14,11 @@ Prints ONE JSON line on rank 0.
 
 Order inside a rank: build -> W warm-up steps -> barrier + synchronize -> K timed steps (nothing but the step and one
 HIP event per step boundary on the launch stream) -> synchronize + barrier -> [rank 0, --dump-outputs DIR: the last
-timed step's loss, forward outputs, updated parameters and gradients to DIR/*.npy] -> [rank 0, N=1: CPU oracle leg] ->
-a separate, untimed pass with HIP events around every matrix-core launch (the roofline families).  `value` is
+timed step's loss, forward outputs, updated parameters and gradients to DIR/*.npy] -> the line.  `value` is
 patches / wall-clock of the K timed steps (max over ranks); `step_ms` gives median / min / max of the K steps.
+With --full, two untimed legs run before the line: [rank 0, N=1, fp32 flavr: CPU oracle leg, `cpu_baseline` and
+`parity_vs_cpu`] -> a separate pass with HIP events around every matrix-core launch (`roofline*`).  A plain run does
+without them: they take longer than the headline's own steps and do not change it.
 """
 import argparse
 import gc
@@ -176,9 +178,14 @@ def main():
                          "flavr_ref = the reference's own stage-1 training shape, UNet_3D_3D(2,..,4,4) on "
                          "(B,2,4,96,96) with the UASR head (configs/brain.yaml)")
     ap.add_argument("--batch", type=int, default=32, help="batch of the flavr_ref workload (brain.yaml: 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=3, help="timed oracle steps of the cpu_baseline leg (after 1 warm-up)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the measurements the headline figure does not need: the CPU oracle "
+                         "leg (cpu_baseline, parity_vs_cpu; rank 0, N=1, fp32 flavr) and the per-kernel timing pass "
+                         "(roofline*, mfma_kernel_ms_per_step, kernel_timing)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle leg")
+    ap.add_argument("--cpu-steps", type=int, default=3,
+                    help="--full: timed oracle steps of the cpu_baseline leg (after 1 warm-up)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-kernel timing pass")
     ap.add_argument("--no-wgrad-stream", action="store_true",
                     help="weight gradients on the main stream (default: PatchParallel launches them on a second HIP stream); "
                          "the per-kernel pass always runs without it, and the rocprofv3 kernel statistics under profiles/ "
@@ -189,7 +196,7 @@ def main():
     ap.add_argument("--no-form-cache", action="store_true",
                     help="frozen networks (cfg4 / cfg5: the teacher) re-pack their weights at every launch too")
     ap.add_argument("--kernel-steps", type=int, default=0,
-                    help="steps of the separate per-kernel timing pass (0: max(--steps, 50), at most 100)")
+                    help="--full: steps of the separate per-kernel timing pass (0: max(--steps, 50), at most 100)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo + --workload stub: the launch / exchange / report plumbing on CPU ranks (tests)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -383,7 +390,7 @@ def main():
     # the CPU leg needs the model's INITIAL weights (host copy now; everything else of that leg -- the HIP forward for
     # the parity line included -- runs after the timed region: a no-grad forward here leaves the caching allocator
     # with blocks that one later training step has to re-malloc, a 40 ms outlier inside the timed region)
-    cpu_leg = world == 1 and not args.no_cpu_baseline and args.workload == "flavr" and not mixed
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline and args.workload == "flavr" and not mixed
     if cpu_leg:
         sd0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     for _ in range(args.warmup):
@@ -443,7 +450,7 @@ def main():
     step_ms = sorted(raw_ms)
     final_loss = float(loss.item())
 
-    # ---- CPU leg (rank 0, N=1, headline workload): the oracle on the host cores with the GPU model's own initial
+    # ---- --full, CPU leg (rank 0, N=1, headline workload): the oracle on the host cores with the GPU model's own initial
     # weights and patch; its warm-up step doubles as the parity check of the HIP forward (north_star: within 1e-3)
     cpu_rec = parity = None
     if cpu_leg:
@@ -461,10 +468,10 @@ def main():
                   "what": "HIP forward vs the CPU oracle's forward on identical (initial) weights / input"}
         del sd0, ref_out, out0
 
-    # ---- per-kernel pass, untimed: HIP events around every matrix-core launch.  Separate from the timed region
+    # ---- --full, per-kernel pass, untimed: HIP events around every matrix-core launch.  Separate from the timed region
     # (the events cost host time per launch) and LAST in the process, after the CPU leg.
     prof, ksteps = {}, 0
-    if not args.no_kernel_timing and not on_cpu:
+    if args.full and not args.no_kernel_timing and not on_cpu:
         ksteps = args.kernel_steps or min(100, max(args.steps, 50))
         pp.set_wgrad_stream(False)                  # one kernel at a time on the chip: un-shared durations
         streams["teacher"] = False

@@ -3,10 +3,10 @@
 # Run from the repo root on the GPU box: bash tools/collect_profiles_r02.sh [part]   (part in: bench stats pmc stream; default all)
 R=$PWD; O=$R/gpurun_out/r2p; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 PART=${1:-all}
-B="--no-cpu-baseline"
+B="--full --no-cpu-baseline"
 prof() { timeout -k 10 300 rocprofv3 "$@"; }
 if [ "$PART" = all ] || [ "$PART" = bench ]; then   # the bench lines of every workload, un-profiled, on this one box
-python3 $R/bench.py > $O/b_flavr_fp32.log 2>&1 || exit 1; tail -1 $O/b_flavr_fp32.log > $O/b_flavr_fp32.json
+python3 $R/bench.py --full > $O/b_flavr_fp32.log 2>&1 || exit 1; tail -1 $O/b_flavr_fp32.log > $O/b_flavr_fp32.json
 for spec in "seg fp32" "cfg4 fp32" "flavr_ref fp32" "flavr bf16" "seg bf16" "cfg4 bf16"; do
   set -- $spec
   python3 $R/bench.py --workload $1 --precision $2 --steps 30 $B > $O/b_$1_$2.log 2>&1 || exit 1; tail -1 $O/b_$1_$2.log > $O/b_$1_$2.json
