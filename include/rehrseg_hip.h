@@ -552,6 +552,38 @@ int rehr_axis_resample_f32(const float* src, float* dst, const int32_t* idx, con
                            int32_t n_in, int32_t n_out, int64_t inner, int32_t taps, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * nnU-Net training augmentation on the device (utils/seg_utils.py:632-728 get_training_transforms as REHRSeg calls
+ * it; rehrseg_amd/utils/augment.py builds the chain).  Batches are dense fp32 [B][...]; per-item parameter records
+ * (fp64) and statistics live in device memory, drawn and uploaded by the host once per batch.
+ * ------------------------------------------------------------------------- */
+#define REHR_AUG_WARP_SPLINE3 0 /* order-3 B-spline over prefiltered coefficients, cval 0 (data, uncertainty) */
+#define REHR_AUG_WARP_LABEL 1   /* batchgenerators interpolate_img(is_seg=True, order=1, cval=-1): label vote */
+#define REHR_AUG_WARP_PARAMS 8  /* doubles per item: R00 R01 R10 R11 scale ctr0 ctr1 (unused) */
+/* dst[b][c][i][j] = sample of src[b][c] (Hi x Wi) at ((p R) * scale + ctr) with p = (i - (Ho-1)/2, j - (Wo-1)/2):
+ * MySpatialTransform (dim 2, no elastic deformation) of every depth slice c with the coordinates of item b. */
+int rehr_aug_warp2d_f32(const float* src, float* dst, const double* params, int32_t B, int32_t C, int32_t Hi,
+                        int32_t Wi, int32_t Ho, int32_t Wo, int32_t mode, void* stream);
+/* stats[b] = {sum, sum of squares, min, max} of x[b][0..S) (fp64); work holds B * REHR_AUG_STAT_PARTS * 4 doubles. */
+#define REHR_AUG_STAT_PARTS 256
+int rehr_aug_stats_f32(const float* x, int32_t B, int64_t S, double* work, double* stats, void* stream);
+/* One intensity step in place over x[b][0..S); params[b][REHR_AUG_PW_PARAMS] = {fires (0: item untouched), a, b, c}:
+ *   NOISE     {1, std, seed}: x += std * N(0, 1) from a counter-based generator of (seed, index)
+ *   SCALE     {1, m}: x *= m
+ *   CONTRAST  {1, f}, stats0 of x: x = clip((x - mean) * f + mean, min, max)
+ *   CLIP      {1}, stats0: x = clip(x, min, max)
+ *   GAMMA     {1, g, s}, stats0 of x: x' = s x, x = ((x' - min') / (rng' + 1e-7))^g * (rng' + 1e-7) + min'
+ *   RETAIN    {1, -, s}, stats0 of x before GAMMA, stats1 of x after it: x = s ((x - mean1) / (sd1 + 1e-8) * sd0' + mean0') */
+#define REHR_AUG_PW_PARAMS 4
+#define REHR_AUG_NOISE 0
+#define REHR_AUG_SCALE 1
+#define REHR_AUG_CONTRAST 2
+#define REHR_AUG_CLIP 3
+#define REHR_AUG_GAMMA 4
+#define REHR_AUG_RETAIN 5
+int rehr_aug_pointwise_f32(float* x, int32_t B, int64_t S, int32_t op, const double* params, const double* stats0,
+                           const double* stats1, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mixed-precision (*_bf16) variants of the HBM-bound fused-block kernels: the SAME arguments as the *_f32 entry
  * points above with every ACTIVATION pointer (x, y, res, dy, dx, dres) addressing bf16 elements (ld* in elements,
  * % 8 == 0, C % 8 == 0); gates, gamma / beta, mean_rstd stay fp32, statistics and reduction buffers fp64, the

@@ -1004,6 +1004,56 @@ def axis_resample(x, axis, idx, w, validated=False):
     return y
 
 
+# ----------------------------------------------------------------------------- training augmentation (augment.hip)
+AUG_WARP_SPLINE3, AUG_WARP_LABEL, AUG_WARP_PARAMS = 0, 1, 8
+AUG_NOISE, AUG_SCALE, AUG_CONTRAST, AUG_CLIP, AUG_GAMMA, AUG_RETAIN = range(6)
+AUG_PW_PARAMS, AUG_STAT_PARTS = 4, 256
+
+
+def _chk_aug(x, *f64):
+    if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+        raise L.RehrsegHipError("augmentation kernels: contiguous float32 device tensors (no CPU fallback)")
+    for t in f64:
+        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise L.RehrsegHipError("augmentation parameters / statistics: contiguous float64 device tensors")
+
+
+def aug_warp2d(src, params, out_hw, mode):
+    """src (B, C, Hi, Wi) -> (B, C, Ho, Wo): the in-plane affine of every slice c of item b with params[b] (float64
+    [B, AUG_WARP_PARAMS] on the device) -- rehr_aug_warp2d_f32."""
+    _chk_aug(src, params)
+    B, Cc, Hi, Wi = src.shape
+    Ho, Wo = (int(v) for v in out_hw)
+    if params.shape != (B, AUG_WARP_PARAMS):
+        raise L.RehrsegHipError("aug_warp2d: one parameter record per item")
+    dst = torch.empty((B, Cc, Ho, Wo), device=src.device, dtype=torch.float32)
+    L.check(L.load().rehr_aug_warp2d_f32(_ptr(src), _ptr(dst), _ptr(params), B, Cc, Hi, Wi, Ho, Wo, int(mode),
+                                         _stream()), "rehr_aug_warp2d_f32")
+    return dst
+
+
+def aug_stats(x, out=None):
+    """x (B, ...) -> float64 (B, 4) {sum, sum of squares, min, max} per item (rehr_aug_stats_f32)."""
+    _chk_aug(x, out)
+    B = x.shape[0]
+    S = x.numel() // B
+    work = torch.empty(B * AUG_STAT_PARTS * 4, device=x.device, dtype=torch.float64)
+    st = torch.empty((B, 4), device=x.device, dtype=torch.float64) if out is None else out
+    L.check(L.load().rehr_aug_stats_f32(_ptr(x), B, S, _ptr(work), _ptr(st), _stream()), "rehr_aug_stats_f32")
+    return st
+
+
+def aug_pointwise(x, op, params, stats0=None, stats1=None):
+    """One intensity step in place over x (B, ...) with params float64 [B, AUG_PW_PARAMS] (rehr_aug_pointwise_f32)."""
+    _chk_aug(x, params, stats0, stats1)
+    B = x.shape[0]
+    if params.shape != (B, AUG_PW_PARAMS):
+        raise L.RehrsegHipError("aug_pointwise: one parameter record per item")
+    L.check(L.load().rehr_aug_pointwise_f32(_ptr(x), B, x.numel() // B, int(op), _ptr(params), _ptr(stats0),
+                                            _ptr(stats1), _stream()), "rehr_aug_pointwise_f32")
+    return x
+
+
 # ----------------------------------------------------------------------------- sr_head.2 on the bf16 matrix cores
 def _thin5_ws(d, dev, f32=False):
     fn = L.load().rehr_conv5_thin_f32_workspace_bytes if f32 else L.load().rehr_conv5_thin_workspace_bytes

@@ -175,6 +175,9 @@ PROTOTYPES = {
     "rehr_conv5_thin_fwd_bf16": (C.c_int, [_P_DC, _vp, _i64, _vp]),
     "rehr_patch_gather": (C.c_int, [C.POINTER(PatchGatherDesc), C.POINTER(PatchItem), _vp]),
     "rehr_axis_resample_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _vp]),
+    "rehr_aug_warp2d_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "rehr_aug_stats_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp]),
+    "rehr_aug_pointwise_f32": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),

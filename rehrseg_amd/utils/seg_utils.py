@@ -17,6 +17,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .augment import MySpatialTransform, get_training_transforms  # noqa: F401  (utils/seg_utils.py:511-728)
+
 
 def zscore_normalization(image):
     """Per-sample z-score of channel 0, IN PLACE on the caller's tensor (ref :137-149);

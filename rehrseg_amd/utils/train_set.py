@@ -13,8 +13,9 @@ What is pinned by fixtures generated from the reference's own classes (tools/gen
 protocol, crop / pad / flip / transposition / zero-slice / permute logic of all three `__getitem__`s.  What is not
 (packages absent offline, restated from their published behaviour, "parity unpinned"): `resize.pytorch.resize`
 (`resize_axis` below), `degrade.select_kernel` (utils/blur_kernel_ops.py of this package), the batchgenerators
-augmentation chain of stage 2 (`train_transform`: pass a callable, default identity), h5py / nibabel containers
-(`.npz` files with the reference's H5 keys are read instead; h5py is used when importable).
+augmentation chain (utils/augment.py: on the device, `train_transform="nnunet"` for stage 2, `nnunet_transform=True` for
+stage 1; the spatial step is pinned, the intensity transforms are not), h5py / nibabel containers (`.npz` files with
+the reference's H5 keys are read instead; h5py is used when importable).
 """
 import math
 import os
@@ -25,7 +26,9 @@ import torch
 
 from .. import hip_backend as hb
 from .pad import get_pads
-from .seg_utils import zscore_normalization
+from .seg_utils import get_training_transforms, zscore_normalization
+
+_ROTATION_FOR_DA = {"x": (-np.pi, np.pi), "y": (0, 0), "z": (0, 0)}  # utils/train_set.py:61, :260
 
 
 # ----------------------------------------------------------------------------- strided views (host integers only)
@@ -326,8 +329,9 @@ class _DeviceSet(torch.utils.data.Dataset):
 class TrainSetMultipleSegSREfficient(_DeviceSet):
     """utils/train_set.py:21-160.  `volumes` (one dict per subject with 'img', 'seg' and, with `uncertainty`,
     'uncertainty' arrays of shape (x, y, z)) replaces the H5 files when given.  `train_transform` stands where the
-    reference calls its batchgenerators chain (:64-84, absent offline): a callable over the keyword tensors
-    data / seg / seg_sr / uncertainty, default identity."""
+    reference calls its batchgenerators chain (:64-84): "nnunet" builds that chain on the device (utils/augment.py;
+    in-plane output `target_patch_size`), a callable over the keyword tensors data / seg / seg_sr / uncertainty is
+    used as given, None (default) is the identity."""
 
     def __init__(self, image_path, split_subjects, slice_thickness, target_thickness, patch_size_ori, target_patch_size,
                  random_flip=False, uncertainty=False, preload=True, norm=True, device=None, volumes=None,
@@ -337,6 +341,14 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
         self.separation = int(slice_thickness / target_thickness)
         self.random_flip, self.uncertainty, self.norm = random_flip, uncertainty, norm
         self.target_patch_size = target_patch_size
+        if isinstance(train_transform, str):
+            if train_transform != "nnunet":
+                raise ValueError(f"train_transform: 'nnunet', a callable or None, got {train_transform!r}")
+            train_transform = get_training_transforms(
+                list(target_patch_size)[::-1], _ROTATION_FOR_DA, None, None, True, order_resampling_data=3,
+                order_resampling_seg=1, use_mask_for_norm=[False], is_cascaded=False, foreground_labels=[1],
+                regions=None, ignore_label=None, enable_uncertainty=uncertainty,
+                extra_keys=["seg", "seg_sr", "uncertainty"] if uncertainty else ["seg", "seg_sr"])
         self.train_transform = train_transform
         self.device = self._check_device(device)
         self.imgs, self.labels, self.uncertainties = [], [], []
@@ -458,8 +470,12 @@ class TrainSetMultiple(_DeviceSet):
         self.all_subjects = split_subjects
         self.slice_thickness, self.target_thickness = slice_thickness, target_thickness
         self.slice_separation = float(slice_thickness / target_thickness)
-        if nnunet_transform:
-            raise NotImplementedError("the nnU-Net augmentation chain (batchgenerators, :260-276) is absent offline")
+        self.train_transform = None
+        if nnunet_transform:  # :259-276: intensity augmentation of the HR image only (enable_spatial=False)
+            self.train_transform = get_training_transforms(
+                patch_size, _ROTATION_FOR_DA, None, None, True, order_resampling_data=3, order_resampling_seg=1,
+                use_mask_for_norm=[False], is_cascaded=False, foreground_labels=[1], regions=None, ignore_label=None,
+                enable_spatial=False, enable_uncertainty=blur, extra_keys=["seg", "img_lr"] if blur else ["seg"])
         self.imgs_hr, self.labels_hr, self.imgs_filtered_x, self.imgs_filtered_y = [], [], [], []
         if volumes is None:
             names = os.listdir(image_path)
@@ -542,29 +558,46 @@ class TrainSetMultiple(_DeviceSet):
     def _run(self, plans):
         ids = [p["i"] for p in plans]
         sep = self.slice_separation
+        aug = None
+        if self.train_transform is not None:
+            # the reference augments the HR patch in its (z, 1, x, y) layout before the LR resize and the tail (:366-380):
+            # gather it untransformed, run the chain, then cut the tail out of the augmented buffer like `low` below
+            pre = _gather([p["hr"] for p in plans], [self.imgs_hr[i] for i in ids])          # (B, z, 1, x, y)
+            aug = self.train_transform(data=pre.permute(0, 2, 1, 3, 4).contiguous())["data"]
+            aug = aug.permute(0, 2, 1, 3, 4).contiguous()
         # HR pair: image and label channels gathered straight into their final orientation
         hr_views = [self._tail(p["hr"], p, False) for p in plans]
-        img_hr = _gather(hr_views, [self.imgs_hr[i] for i in ids])
+        if aug is None:
+            img_hr = _gather(hr_views, [self.imgs_hr[i] for i in ids])
+        else:
+            img_hr = _gather(self._slabs([self._tail(View(aug.shape[1:]), p, False) for p in plans], aug),
+                             [aug] * len(plans))
         lab_hr = _gather(hr_views, [self.labels_hr[i] for i in ids])
         out_hr = torch.cat((img_hr, lab_hr), dim=1)
         # LR pair: blurred patch (z, 1, x, y) -> cubic down-sampling along x -> final orientation; the order-0 label is
-        # a strided gather of the label volume itself
-        src = [p["lr_src"] if self.blur else self.imgs_hr[p["i"]] for p in plans]
-        patch = _gather([p["lr"] for p in plans], src)                       # (B, z, 1, x, y)
+        # a strided gather of the label volume itself.  Without blur the LR image derives from the (augmented) HR patch.
+        if not self.blur and aug is not None:
+            patch = aug
+        else:
+            src = [p["lr_src"] if self.blur else self.imgs_hr[p["i"]] for p in plans]
+            patch = _gather([p["lr"] for p in plans], src)                   # (B, z, 1, x, y)
         low = resize_axis(patch, 3, sep, 3)                                  # (B, z, 1, x / sep, y)
         idx0, _ = resize_taps(plans[0]["hr"].shape[2], sep, 0)
         lr_views, lab_views = [], []
         for b, p in enumerate(plans):
             lr_views.append(self._tail(View(low.shape[1:]), p, True))
             lab_views.append(self._tail(_take(p["hr"], 2, idx0[:, 0]), p, True))
-        # every item reads its own slab of `low`
-        slab = low[0].numel()
-        items_src = [low] * len(plans)
-        for b, v in enumerate(lr_views):
-            v.base += b * slab
-        img_lr = _gather(lr_views, items_src)
+        img_lr = _gather(self._slabs(lr_views, low), [low] * len(plans))
         lab_lr = _gather(lab_views, [self.labels_hr[i] for i in ids])
         return torch.cat((img_lr, lab_lr), dim=1), out_hr
+
+    @staticmethod
+    def _slabs(views, buf):
+        """every item reads its own slab of the batch buffer `buf`"""
+        slab = buf[0].numel()
+        for b, v in enumerate(views):
+            v.base += b * slab
+        return views
 
 
 def _take(v, axis, idx):
