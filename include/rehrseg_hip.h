@@ -584,6 +584,32 @@ int rehr_aug_pointwise_f32(float* x, int32_t B, int64_t S, int32_t op, const dou
                            const double* stats1, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Stage-2 validation on the device (utils/seg_utils.py:240-287 tiled predictor with mirror TTA, :736-784
+ * evaluate_case; rehrseg_amd/utils/seg_utils.py drives them).  fp16 accumulators as the reference's; every rounding
+ * equals torch's on the same operands (csrc/seg_eval.hip).
+ * ------------------------------------------------------------------------- */
+/* out (8, 1, d, h, w) fp32 = the tile at (start_d, start_h, start_w) of the volume vol (D, H, W) constant-padded by
+ * (pad_d, pad_h, pad_w) voxels below (zeros outside vol), as the identity then the mirrorings of the axes
+ * (d), (h), (w), (d,h), (d,w), (h,w), (d,h,w). */
+int rehr_tta_gather_f32(const float* vol, float* out, int32_t D, int32_t H, int32_t W, int32_t pad_d, int32_t pad_h,
+                        int32_t pad_w, int32_t start_d, int32_t start_h, int32_t start_w, int32_t d, int32_t h,
+                        int32_t w, void* stream);
+/* pred: fp32 (8, C, d, h, w) with element strides[5] (any layout, >= 0).  For every voxel of the tile and every c:
+ * p = ((pred[0] + unflip(pred[1])) + ...) + unflip(pred[7]), p = p / 8, logits[c][od+i][oh+j][ow+k] += p * g and
+ * counts[od+i][oh+j][ow+k] += g in fp32, each rounded once to fp16; g = gaussian[i][j][k] (fp16 (d, h, w)), or 1 when
+ * gaussian is NULL.  logits: fp16 [C][Do][Ho][Wo], counts: fp16 [Do][Ho][Wo]. */
+int rehr_tta_blend_f16acc(const float* pred, const int64_t* strides, int32_t C, int32_t d, int32_t h, int32_t w,
+                          const void* gaussian, void* logits, void* counts, int32_t Do, int32_t Ho, int32_t Wo,
+                          int32_t od, int32_t oh, int32_t ow, void* stream);
+/* logits fp16 [2][D][H][W] /= counts fp16 [D][H][W] in place (fp32 quotient rounded to fp16); stats[0] is set to 1 if
+ * any quotient is +-inf.  labels (NULL: skipped) [CD][CH][CW] uint8 = argmax over the 2 classes (ties: class 0) inside
+ * the crop at (crop_d, crop_h, crop_w); with gt (uint8, the crop's shape) stats[1..3] += sum(p * gt), sum(p), sum(gt).
+ * stats: 4 uint64, zeroed by the caller. */
+int rehr_seg_eval_finalize_f16(void* logits, const void* counts, int32_t D, int32_t H, int32_t W, int32_t crop_d,
+                               int32_t crop_h, int32_t crop_w, int32_t CD, int32_t CH, int32_t CW, uint8_t* labels,
+                               const uint8_t* gt, uint64_t* stats, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mixed-precision (*_bf16) variants of the HBM-bound fused-block kernels: the SAME arguments as the *_f32 entry
  * points above with every ACTIVATION pointer (x, y, res, dy, dx, dres) addressing bf16 elements (ld* in elements,
  * % 8 == 0, C % 8 == 0); gates, gamma / beta, mean_rstd stay fp32, statistics and reduction buffers fp64, the

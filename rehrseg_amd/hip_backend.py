@@ -1054,6 +1054,75 @@ def aug_pointwise(x, op, params, stats0=None, stats1=None):
     return x
 
 
+# ----------------------------------------------------------------------------- stage-2 validation (seg_eval.hip)
+def _chk_eval(t, dtype, what, dim=None):
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (dim is not None and t.dim() != dim):
+        raise L.RehrsegHipError(f"{what}: contiguous {dtype} device tensor" + (f" of {dim} dims" if dim else "") +
+                                " (no CPU fallback)")
+
+
+def tta_gather(vol, pad, start, tile, out=None):
+    """vol (D, H, W) fp32, constant-padded by `pad` voxels below -> the (8, 1, d, h, w) TTA batch of the tile at
+    `start` (padded coordinates): identity, then the mirrorings in itertools.combinations order (rehr_tta_gather_f32)."""
+    _chk_eval(vol, torch.float32, "tta_gather volume", 3)
+    d, h, w = (int(v) for v in tile)
+    if out is None:
+        out = torch.empty((8, 1, d, h, w), device=vol.device, dtype=torch.float32)
+    elif tuple(out.shape) != (8, 1, d, h, w):
+        raise L.RehrsegHipError("tta_gather: out must be (8, 1) + tile")
+    _chk_eval(out, torch.float32, "tta_gather out")
+    L.check(L.load().rehr_tta_gather_f32(_ptr(vol), _ptr(out), *vol.shape, *(int(v) for v in pad),
+                                         *(int(v) for v in start), d, h, w, _stream()), "rehr_tta_gather_f32")
+    return out
+
+
+def tta_blend(pred, logits, counts, start, gaussian=None):
+    """Un-mirror the network's (8, C, d, h, w) fp32 output (any strides), average, weight and add it into the fp16
+    accumulators logits [C, D, H, W] / counts [D, H, W] at `start` (rehr_tta_blend_f16acc)."""
+    if not pred.is_cuda or pred.dtype != torch.float32 or pred.dim() != 5 or pred.shape[0] != 8:
+        raise L.RehrsegHipError("tta_blend: the prediction is an (8, C, d, h, w) float32 device tensor")
+    _chk_eval(logits, torch.float16, "tta_blend logits", 4)
+    _chk_eval(counts, torch.float16, "tta_blend counts", 3)
+    C_, d, h, w = pred.shape[1:]
+    if logits.shape[0] != C_ or tuple(logits.shape[1:]) != tuple(counts.shape):
+        raise L.RehrsegHipError("tta_blend: logits [C, D, H, W] and counts [D, H, W] of the prediction's C")
+    if gaussian is not None:
+        _chk_eval(gaussian, torch.float16, "tta_blend gaussian", 3)
+        if tuple(gaussian.shape) != (d, h, w):
+            raise L.RehrsegHipError("tta_blend: the Gaussian has the tile's shape")
+    strides = (C.c_int64 * 5)(*pred.stride())
+    L.check(L.load().rehr_tta_blend_f16acc(_ptr(pred), strides, C_, d, h, w, _ptr(gaussian), _ptr(logits),
+                                           _ptr(counts), *counts.shape, *(int(v) for v in start), _stream()),
+            "rehr_tta_blend_f16acc")
+
+
+def seg_eval_finalize(logits, counts, stats, crop=None, labels=None, gt=None):
+    """logits [2, D, H, W] /= counts in place; stats (int64 [4], zeroed): [0] set on an inf, [1..3] += the Dice terms
+    sum(p * gt), sum(p), sum(gt) against gt; labels (uint8, the crop's shape) = the argmax inside `crop`, a tuple of
+    slices of (D, H, W) (None: the whole volume) (rehr_seg_eval_finalize_f16)."""
+    _chk_eval(logits, torch.float16, "seg_eval_finalize logits", 4)
+    _chk_eval(counts, torch.float16, "seg_eval_finalize counts", 3)
+    _chk_eval(stats, torch.int64, "seg_eval_finalize stats", 1)
+    if logits.shape[0] != 2:
+        raise L.RehrsegHipError("seg_eval_finalize: 2 classes")
+    if tuple(logits.shape[1:]) != tuple(counts.shape) or stats.numel() < 4:
+        raise L.RehrsegHipError("seg_eval_finalize: counts [D, H, W] of the logits, 4 stats")
+    dims = tuple(counts.shape)
+    crop = crop or tuple(slice(None) for _ in dims)
+    lo, size = [], []
+    for sl, n in zip(crop, dims):
+        a, b, _ = sl.indices(n)
+        lo.append(a)
+        size.append(b - a)
+    for t, what in ((labels, "labels"), (gt, "gt")):
+        if t is not None:
+            _chk_eval(t, torch.uint8, f"seg_eval_finalize {what}", 3)
+            if tuple(t.shape) != tuple(size):
+                raise L.RehrsegHipError(f"seg_eval_finalize: {what} has the crop's shape {tuple(size)}")
+    L.check(L.load().rehr_seg_eval_finalize_f16(_ptr(logits), _ptr(counts), *dims, *lo, *size, _ptr(labels), _ptr(gt),
+                                                _ptr(stats), _stream()), "rehr_seg_eval_finalize_f16")
+
+
 # ----------------------------------------------------------------------------- sr_head.2 on the bf16 matrix cores
 def _thin5_ws(d, dev, f32=False):
     fn = L.load().rehr_conv5_thin_f32_workspace_bytes if f32 else L.load().rehr_conv5_thin_workspace_bytes

@@ -178,6 +178,9 @@ PROTOTYPES = {
     "rehr_aug_warp2d_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "rehr_aug_stats_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp]),
     "rehr_aug_pointwise_f32": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "rehr_tta_gather_f32": (C.c_int, [_vp, _vp] + [_i32] * 12 + [_vp]),
+    "rehr_tta_blend_f16acc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
+    "rehr_seg_eval_finalize_f16": (C.c_int, [_vp, _vp] + [_i32] * 9 + [_vp, _vp, _vp, _vp]),
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),

@@ -4,6 +4,7 @@ pass, on the MI355X modules.
   get_intermediate_features   train_all.py:85-112   (teacher features for distillation)
   train_sr_step               train_all.py:118-139  (stage 1b/1c: FLAVR self-SR step)
   train_segsr_step            train_all.py:521-556  (stage 2: SegModel + distillation step)
+  evaluate / evaluate_cases   train_all.py:154-193  (stage-2 validation, evaluate_case on the device)
 
 Results are those of the reference loops; two things are restructured for the GPU:
   * the teacher's D-1 four-slice windows are ONE batched encoder call instead of D-1
@@ -11,6 +12,7 @@ Results are those of the reference loops; two things are restructured for the GP
   * `levels` lets the caller stop the teacher after the level it consumes (the stage-2
     loop only reads level 1).
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -152,3 +154,69 @@ def train_segsr_step(model_seg, model_sr, distiller, opt, img, label_lr, label_h
         grad_sync()
     opt.step()
     return loss
+
+
+def _report(dice, terms):
+    """train_all.py:188-193's summary; the global Dice from the summed exact per-case terms."""
+    from .utils.seg_utils import _dice_from_counts
+    tot = [sum(t[k] for t in terms) for k in range(3)]
+    print(f"Global dice: {_dice_from_counts(*tot)}")
+    print(f"Average dice: {sum(dice) / len(dice)}")
+    print(f"Std dice: {np.std(dice)}")
+    print(f"Max dice: {max(dice)}")
+    print(f"Min dice: {min(dice)}")
+    return sum(dice) / len(dice)
+
+
+def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1, *, device=None):
+    """train_all.py:154-193 over in-memory cases: `cases` yields (name, image, label), each a (1, D, H, W) array or
+    tensor (or a file name).  Prints the reference's summary and returns the mean Dice.
+
+    The global Dice is calculate_dice over the concatenated LR maps, formed from the summed per-case integer terms, so
+    no map is kept.  (The reference concatenates float32 label tensors, so its float32 sums can differ from these
+    exact ones in the last bits once the counts pass 2**24.)  `device`: as evaluate_case's."""
+    from .utils.seg_utils import _evaluate_case
+    dice, terms = [], []
+    for name, img, label in cases:
+        out = _evaluate_case(model_seg, img, label, seperation, patch_size_ori[::-1], eval_HR, device)
+        print(f"Subject {name}: {out[3]}")
+        dice.append(out[3])
+        terms.append(out[4])
+    return _report(dice, terms)
+
+
+def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path, fold, save_path=None, eval_HR=False,
+             seperation=1):
+    """train_all.py:154-193: every validation subject of the split's fold, read with SimpleITK; with `save_path`, the
+    predictions are written next to it as NIfTI via SimpleITK as the reference does."""
+    import json
+    import os
+    from .utils.seg_utils import _evaluate_case, _sitk
+    sitk = _sitk()
+    with open(split_path, "r") as f:
+        split_data = json.load(f)[fold]["val"]
+    dice, terms = [], []
+    for subject in split_data:
+        test_img = os.path.join(val_img_path, subject + "_0000.nii.gz")
+        test_label = os.path.join(val_label_path, subject + ".nii.gz")
+        pred_lr, pred_hr, _, dice_lr, t = _evaluate_case(model_seg, test_img, test_label, seperation,
+                                                          patch_size_ori[::-1], eval_HR)
+        if save_path is not None:
+            os.makedirs(os.path.join(save_path, "val"), exist_ok=True)
+            ori = sitk.ReadImage(test_img)
+            img = sitk.GetImageFromArray(pred_lr)
+            img.SetSpacing(ori.GetSpacing())
+            img.SetOrigin(ori.GetOrigin())
+            img.SetDirection(ori.GetDirection())
+            sitk.WriteImage(img, os.path.join(save_path, "val", f"{subject}_pred_lr.nii.gz"))
+            if eval_HR:
+                img = sitk.GetImageFromArray(pred_hr)
+                sp = ori.GetSpacing()
+                img.SetSpacing([sp[0], sp[1], sp[2] / seperation])
+                img.SetOrigin(ori.GetOrigin())
+                img.SetDirection(ori.GetDirection())
+                sitk.WriteImage(img, os.path.join(save_path, "val", f"{subject}_pred_hr.nii.gz"))
+        print(f"Subject {subject}: {dice_lr}")
+        dice.append(dice_lr)
+        terms.append(t)
+    return _report(dice, terms)

@@ -6,7 +6,9 @@ _build_loss) and :786-885 (DiceLoss, BCEDiceLoss).
 The stage-2 loss (`DC_and_weighted_CE_loss`) runs as one fused HIP pass over the logits each way when
 given device tensors (`_FusedDCCE`); the torch composition below it is the same
 arithmetic and is what the CPU-side tests and the oracle comparisons evaluate.  The tiled predictor
-helpers at the end of the file mirror utils/seg_utils.py:176-287.
+helpers at the end of the file mirror utils/seg_utils.py:176-287, and the validation
+after them (:45-72, :158-174, :730-784: read_image, preprocess_image, calculate_dice, evaluate_case) runs a case on
+the device through csrc/seg_eval.hip.
 `MemoryEfficientSoftDiceLoss` lives in nnunetv2==2.3.1 (absent offline): its published
 formula is restated in `SoftDiceLoss` below -- that term's parity is unpinned.
 """
@@ -338,3 +340,235 @@ def _internal_predict_sliding_window_return_logits(data, slicers, network, do_on
     if use_gaussian:
         compute_gaussian.cache_clear()
     return predicted_logits
+
+
+# ----------------------------------------------------------------------------- stage-2 validation
+# (ref utils/seg_utils.py:45-72 read_image, :158-174 preprocess_image, :730-784 calculate_dice / evaluate_case)
+def calculate_dice(prediction, ground_truth, smooth=1e-5):
+    """ref :730-734."""
+    prediction = prediction.flatten()
+    ground_truth = ground_truth.flatten()
+    intersection = np.sum(prediction * ground_truth)
+    return (2. * intersection + smooth) / (np.sum(prediction) + np.sum(ground_truth) + smooth)
+
+
+def _dice_from_counts(intersection, sum_pred, sum_gt, smooth=1e-5):
+    """calculate_dice of two uint8 maps from their exact integer sums (numpy's uint64 accumulators)."""
+    intersection, sum_pred, sum_gt = np.uint64(intersection), np.uint64(sum_pred), np.uint64(sum_gt)
+    return (2. * intersection + smooth) / (sum_pred + sum_gt + smooth)
+
+
+def _sitk():
+    try:
+        import SimpleITK as sitk
+    except ImportError as e:
+        raise ImportError("reading or writing image files needs SimpleITK, which is not installed; pass the volume as "
+                          "an array or tensor of shape (1, D, H, W) instead") from e
+    return sitk
+
+
+def read_image(image_fname):
+    """ref :45-72: (float32 (1, D, H, W) array, {'sitk_stuff': ..., 'spacing': (z, y, x)})."""
+    sitk = _sitk()
+    itk_image = sitk.ReadImage(image_fname)
+    spacing, origin, direction = itk_image.GetSpacing(), itk_image.GetOrigin(), itk_image.GetDirection()
+    npy_image = sitk.GetArrayFromImage(itk_image)
+    if npy_image.ndim != 3:
+        raise RuntimeError(f"Unexpected number of dimensions: {npy_image.ndim} in file {image_fname}")
+    props = {"sitk_stuff": {"spacing": spacing, "origin": origin, "direction": direction},
+             "spacing": list(np.abs(list(spacing)[::-1]))}
+    return npy_image[None].astype(np.float32), props
+
+
+def preprocess_image(image_file, apply_norm=True):
+    """ref :158-174: a file name (SimpleITK) or an array / tensor of shape (1, D, H, W) -> (float32 CPU tensor
+    (1, D, H, W), properties).  The z-score runs on the host in numpy, as the reference's."""
+    if isinstance(image_file, (np.ndarray, torch.Tensor)):
+        data = image_file.detach().cpu().numpy() if isinstance(image_file, torch.Tensor) else image_file
+        if data.ndim != 4 or data.shape[0] != 1:
+            raise ValueError(f"expected a (1, D, H, W) volume, got {tuple(data.shape)}")
+        data, properties = np.asarray(data).astype(np.float32), {}
+    else:
+        data, properties = read_image(image_file)
+    data = np.copy(data)
+    if apply_norm:
+        data = zscore_normalization(data)
+    return torch.from_numpy(data).contiguous().float(), properties
+
+
+def _pad_geometry(shape, new_shape):
+    """acvl_utils pad_nd_image's geometry: (padded shape, pad below, pad above) of `shape` grown to at least
+    `new_shape` (leading axes not named keep their size)."""
+    shape = [int(s) for s in shape]
+    new_shape = list(shape[:len(shape) - len(new_shape)]) + [int(s) for s in new_shape]
+    padded = [max(n, o) for n, o in zip(new_shape, shape)]
+    below = [(p - o) // 2 for p, o in zip(padded, shape)]
+    above = [p - o - b for p, o, b in zip(padded, shape, below)]
+    return padded, below, above
+
+
+def pad_nd_image(image, new_shape=None, mode="constant", kwargs=None, return_slicer=False,
+                 shape_must_be_divisible_by=None):
+    """acvl_utils pad_nd_image, restated (absent offline -> parity unpinned) for what REHRSeg passes: pad to at least
+    `new_shape` with pad_below = diff // 2, pad_above = diff - pad_below; with return_slicer, also the slicer that
+    reverts the padding."""
+    if new_shape is None or shape_must_be_divisible_by is not None:
+        raise NotImplementedError("pad_nd_image: REHRSeg passes a new_shape and no divisibility constraint")
+    padded, below, above = _pad_geometry(image.shape, new_shape)
+    pad_list = list(zip(below, above))
+    if any(below) or any(above):
+        if isinstance(image, np.ndarray):
+            res = np.pad(image, pad_list, mode, **(kwargs or {}))
+        else:
+            res = F.pad(image, [v for p in pad_list[::-1] for v in p], mode, **(kwargs or {}))
+    else:
+        res = image
+    if not return_slicer:
+        return res
+    return res, tuple(slice(b, p - a) for b, a, p in zip(below, above, padded))
+
+
+def _integral_separation(slice_separation):
+    sep = float(slice_separation)
+    if not sep.is_integer() or sep < 1:
+        raise ValueError(f"slice_separation must be a positive integer, got {slice_separation!r}")
+    return int(sep)
+
+
+@functools.lru_cache(maxsize=4)
+def _device_gaussian(tile, device):
+    """compute_gaussian's fp16 importance map (the predictor's arguments) built on the host and uploaded without a
+    host sync; kept for the next case."""
+    g = compute_gaussian(tuple(tile), sigma_scale=1. / 8, value_scaling_factor=10, device="cpu")
+    return _upload(g, torch.device(device))
+
+
+def _upload(t, dev):
+    if dev.type != "cuda":
+        return t.to(dev)
+    return t.pin_memory().to(dev, non_blocking=True)
+
+
+def _to_host(t):
+    if not t.is_cuda:
+        return t
+    out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    out.copy_(t, non_blocking=True)
+    return out
+
+
+def _fused_tiles(vol, pad, slicers, network, out_idx, deep_supervision, sep, gaussian):
+    """The tile loop of the tiled predictor on the device: per tile one gather of the 8-variant batch, one forward,
+    one blend into the fp16 accumulators.  Returns (logits, counts) before the normalisation; no host sync."""
+    from .. import ops
+    be = ops.get_backend()
+    D, H, W = (int(n) for n in _slicers_extent(slicers))
+    logits = torch.zeros((2, D * sep, H, W), dtype=torch.half, device=vol.device)
+    counts = torch.zeros((D * sep, H, W), dtype=torch.half, device=vol.device)
+    batch = None
+    for sl in slicers:
+        start = [s.start for s in sl[1:]]
+        tile = [s.stop - s.start for s in sl[1:]]
+        reuse = batch is not None and tuple(batch.shape[2:]) == tuple(tile)   # stream order keeps this safe
+        batch = be.tta_gather(vol, pad, start, tile, out=batch if reuse else None)
+        pred = network(batch)
+        if out_idx is not None:
+            pred = pred[out_idx]
+            if out_idx == 0 and deep_supervision:
+                pred = pred[0]
+        if pred.shape[1] != 2:
+            raise NotImplementedError("the fused predictor accumulates 2 classes, as the reference's predictor does")
+        if tuple(pred.shape[2:]) != (tile[0] * sep, tile[1], tile[2]):
+            raise ValueError(f"network output {tuple(pred.shape)} does not cover the tile {tile} x {sep} in depth")
+        if pred.dtype != torch.float32:  # bf16 under ops.mixed_precision(): blended in fp32
+            pred = pred.float()
+        be.tta_blend(pred, logits, counts, (start[0] * sep, start[1], start[2]), gaussian)
+    return logits, counts
+
+
+def _slicers_extent(slicers):
+    """The spatial extent (D, H, W) the sliding-window slicers cover (the padded volume)."""
+    return [max(sl[k].stop for sl in slicers) for k in range(1, 4)]
+
+
+def _check_inf(flag):
+    if flag:
+        raise RuntimeError("Encountered inf in predicted array. Aborting... If this problem persists, reduce "
+                           "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32")
+
+
+def _fused_predict_sliding_window_return_logits(data, slicers, network, out_idx=None, slice_seperation=1,
+                                                patch_size=[14, 320, 384], use_gaussian=False, deep_supervision=True,
+                                                pad=(0, 0, 0)):
+    """_internal_predict_sliding_window_return_logits with the per-tile and the final work in HIP kernels: the same
+    normalised fp16 logits, bit for bit.  `data` (1, D, H, W) on the device is the volume before the constant padding
+    of `pad` voxels below (the slicers address the padded volume); the padded copy is never built."""
+    from .. import ops
+    vol = data[0].to(torch.float32).contiguous()
+    gaussian = _device_gaussian(tuple(int(p) for p in patch_size), str(vol.device)) if use_gaussian else None
+    logits, counts = _fused_tiles(vol, pad, slicers, network, out_idx, deep_supervision, int(slice_seperation),
+                                  gaussian)
+    stats = torch.zeros(4, dtype=torch.int64, device=vol.device)
+    ops.get_backend().seg_eval_finalize(logits, counts, stats)
+    _check_inf(int(stats[0]))
+    return logits
+
+
+def _model_device(model):
+    for t in list(model.parameters()) + list(model.buffers()):
+        return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, device=None):
+    """evaluate_case, plus the exact Dice terms (intersection, sum of the prediction, sum of the label)."""
+    from .. import ops
+    be = ops.get_backend()
+    model.eval()
+    sep = _integral_separation(slice_separation)
+    dev = torch.device(device) if device is not None else _model_device(model)
+    lr_data, _ = preprocess_image(case_img)
+    lr_label, _ = preprocess_image(case_label, apply_norm=False)
+    patch = [int(p) for p in patch_size]
+    padded, pad, _ = _pad_geometry(lr_data.shape[1:], patch)
+    revert = tuple(slice(b, b + n) for b, n in zip(pad, lr_data.shape[1:]))
+    vol = _upload(lr_data[0], dev)
+    gt = _upload(torch.from_numpy(lr_label.squeeze(0).numpy().astype("uint8")), dev)
+    slicers = _internal_get_sliding_window_slicers(padded, patch_size=patch)
+    stats = torch.zeros((2, 4), dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        logits, counts = _fused_tiles(vol, pad, slicers, model, 0, False, 1, _device_gaussian(tuple(patch), str(dev)))
+        labels_lr = torch.empty(tuple(gt.shape), dtype=torch.uint8, device=dev)
+        be.seg_eval_finalize(logits, counts, stats[0], revert, labels_lr, gt)
+        del logits, counts
+        lr_host = _to_host(labels_lr)
+        if get_HR_results:
+            # the reference's HR branch: no Gaussian, no softmax, and the padding is not reverted
+            logits, counts = _fused_tiles(vol, pad, slicers, model, 1, True, sep, None)
+            labels_hr = torch.empty(tuple(counts.shape), dtype=torch.uint8, device=dev)
+            be.seg_eval_finalize(logits, counts, stats[1], None, labels_hr)
+            del logits, counts
+            hr_host = _to_host(labels_hr)
+    st = stats.cpu().numpy()  # the one host sync of the case: after it the label maps are on the host as well
+    _check_inf(st[0, 0] or st[1, 0])
+    prediction_lr = lr_host.numpy()
+    prediction_hr = hr_host.numpy() if get_HR_results else prediction_lr
+    terms = tuple(int(v) for v in st[0, 1:])
+    return prediction_lr, prediction_hr, lr_label, _dice_from_counts(*terms), terms
+
+
+def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, *, device=None):
+    """ref :736-784 on the device: (prediction_lr uint8 (D, H, W), prediction_hr, lr_label float (1, D, H, W) CPU
+    tensor, dice_lr float64).
+
+    `case_img` / `case_label` are file names (SimpleITK) or (1, D, H, W) arrays / tensors.  The z-score runs on the host
+    as the reference's; then every tile is one gather of the 8 mirrorings, one forward of that batch and one blend into
+    the fp16 accumulators, and one finalize normalises, checks for inf, takes the argmax inside the un-padding crop and
+    counts the Dice terms.  The case makes one host sync, which reads the inf flag and the counts.
+
+    Deviations: the network runs in the caller's mode (fp32, or bf16 inside ops.mixed_precision()); the reference's
+    torch.autocast fp16 region has no effect on the HIP kernels and is not opened.  The argmax is taken on the fp16
+    logits instead of their fp32 softmax: the same class except for two logits within one fp16 ulp of each other,
+    where exp rounding can make the softmax tie.  `slice_separation` must be integral (ValueError otherwise).
+    `device` defaults to the model's."""
+    return _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results, device)[:4]
