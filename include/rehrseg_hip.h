@@ -610,6 +610,37 @@ int rehr_seg_eval_finalize_f16(void* logits, const void* counts, int32_t D, int3
                                const uint8_t* gt, uint64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Stage-1 -> stage-2 volume handoff on the device (utils/sr_utils.py:137-242 inference_flavr, :279-304 zeroonenorm /
+ * postprocess_flavr; rehrseg_amd/utils/sr_utils.py drives them, csrc/sr_volume.hip).
+ * A "minmax" buffer is two uint32 codes {min, max} that order like the floats they stand for:
+ * code(f) = bits(f) ^ 0x80000000 for f >= +0, ~bits(f) below; the caller initialises it to {0xffffffff, 0} and the
+ * kernels fold values in with atomicMin / atomicMax (order-independent, deterministic).
+ * ------------------------------------------------------------------------- */
+/* minmax <- min / max of x[0..n) folded into its current content (no NaN). */
+int rehr_minmax_f32(const float* x, int64_t n, uint32_t* minmax, void* stream);
+/* vol: the stored (X, Y, Z, C) fp32 volume, C in {1, 2}.  out: the network input of the windows [w0, w0 + b) of
+ * apply_to_vol_flavr (window w reads the slices w-1 .. w+2; a slice outside the volume is zero; Z == 2: -2 .. 1),
+ * logical (b, C, 4, Xp, Yp) in NDHWC memory: out[bi][s][x][y][c] = vol[x][y][z][c], zero for x >= X or y >= Y.
+ * Xp, Yp: multiples of 16; out 16-byte aligned. */
+int rehr_sr_window_gather_f32(const float* vol, float* out, int32_t X, int32_t Y, int32_t Z, int32_t C, int32_t w0,
+                              int32_t b, int32_t Xp, int32_t Yp, void* stream);
+/* net: the network's fp32 (b, C, n_out, >= X, >= Y) output for the windows [w0, w0 + b) of n_windows, element
+ * strides[5] (any layout, >= 0).  With v(c) = net[bi][c][s][x][y] * (max - min) + min (two roundings; min / max
+ * decoded from in_minmax): img[(w0 + bi) * n_out + s][y][x] = v(0); seg (NULL: skipped; needs C >= 2) = v(1) > 0;
+ * out_minmax folds in the written img values.  img / seg: (n_windows * n_out, Y, X); with X % 4 == 0 img must be
+ * 16-byte and seg 4-byte aligned. */
+int rehr_sr_volume_scatter_f32(const float* net, const int64_t* strides, int32_t b, int32_t C, int32_t n_out, int32_t X,
+                               int32_t Y, int32_t w0, int32_t n_windows, const uint32_t* in_minmax, float* img,
+                               uint8_t* seg, uint32_t* out_minmax, void* stream);
+/* out[x][p] = sum_t taps[t] * n(img[x + t - (L - 1) / 2][p]) over the terms inside [0, X), with
+ * n(v) = ((v - min) / (max - min)) * 255 (three roundings): zeroonenorm and the slice-profile blur along the first
+ * axis of postprocess_flavr.  img, out: (X, P) fp32, distinct; taps: L <= 32 device floats (REHR_ENOSUP above). */
+int rehr_stage2_prep_f32(const float* img, const uint32_t* minmax, const float* taps, int32_t L, float* out, int32_t X,
+                         int64_t P, void* stream);
+/* out[i] = low 8 bits of (int32)(n(u[i]) * 255), truncated toward zero: (zeroonenorm(u) * 255).astype('uint8'). */
+int rehr_stage2_unc_u8_f32(const float* u, const uint32_t* minmax, uint8_t* out, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mixed-precision (*_bf16) variants of the HBM-bound fused-block kernels: the SAME arguments as the *_f32 entry
  * points above with every ACTIVATION pointer (x, y, res, dy, dx, dres) addressing bf16 elements (ld* in elements,
  * % 8 == 0, C % 8 == 0); gates, gamma / beta, mean_rstd stay fp32, statistics and reduction buffers fp64, the

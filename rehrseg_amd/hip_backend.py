@@ -1123,6 +1123,99 @@ def seg_eval_finalize(logits, counts, stats, crop=None, labels=None, gt=None):
                                                 _ptr(stats), _stream()), "rehr_seg_eval_finalize_f16")
 
 
+# ----------------------------------------------------------------------------- stage-1 -> stage-2 handoff (sr_volume.hip)
+def minmax_new(device, pairs=1):
+    """`pairs` empty {min, max} code pairs (int32 storage of the kernels' order-preserving uint32 codes)."""
+    mm = torch.empty(2 * pairs, device=device, dtype=torch.int32)
+    mm[0::2].fill_(-1)   # 0xffffffff: above every code
+    mm[1::2].zero_()
+    return mm
+
+
+def minmax_decode(mm):
+    """The float32 values behind a buffer of min / max codes (device arithmetic, no host read)."""
+    return torch.where(mm < 0, mm & 0x7FFFFFFF, ~mm).view(torch.float32)
+
+
+def _chk_mm(mm, what):
+    if not mm.is_cuda or mm.dtype != torch.int32 or mm.numel() != 2 or not mm.is_contiguous():
+        raise L.RehrsegHipError(f"{what}: a {{min, max}} code pair (2 x int32 on the device)")
+
+
+def minmax(x, out=None):
+    """Fold min / max of the float32 device tensor x into the code pair `out` (a fresh one by default)
+    (rehr_minmax_f32)."""
+    _chk_eval(x, torch.float32, "minmax input")
+    if out is None:
+        out = minmax_new(x.device)
+    _chk_mm(out, "minmax out")
+    L.check(L.load().rehr_minmax_f32(_ptr(x), x.numel(), _ptr(out), _stream()), "rehr_minmax_f32")
+    return out
+
+
+def sr_window_gather(vol, w0, b):
+    """vol (X, Y, Z, C) fp32 -> the network input of the windows [w0, w0 + b) of apply_to_vol_flavr: logical
+    (b, C, 4, Xp, Yp), NDHWC memory, in-plane zero-padded to multiples of 16 (rehr_sr_window_gather_f32)."""
+    _chk_eval(vol, torch.float32, "sr_window_gather volume", 4)
+    X, Y, Z, Cc = vol.shape
+    w0, b = int(w0), int(b)
+    if Cc not in (1, 2) or Z < 2 or w0 < 0 or b < 1 or w0 + b > Z - 1:
+        raise L.RehrsegHipError(f"sr_window_gather: windows [{w0}, {w0 + b}) of a {tuple(vol.shape)} volume")
+    Xp, Yp = X + (-X) % 16, Y + (-Y) % 16
+    out = torch.empty((b, 4, Xp, Yp, Cc), device=vol.device, dtype=torch.float32)
+    L.check(L.load().rehr_sr_window_gather_f32(_ptr(vol), _ptr(out), X, Y, Z, Cc, w0, b, Xp, Yp, _stream()),
+            "rehr_sr_window_gather_f32")
+    return out.permute(0, 4, 1, 2, 3)
+
+
+def sr_volume_scatter(net, in_minmax, w0, img, seg, out_minmax):
+    """The network output net (b, C, n_out, >= X, >= Y) fp32 (any strides) of the windows from w0 on -> its slices of
+    img (Zo, Y, X) fp32 after inv_normalize with the input's min / max codes, seg (uint8, or None) = channel 1 > 0, and
+    the min / max of what was written folded into out_minmax (rehr_sr_volume_scatter_f32)."""
+    if not net.is_cuda or net.dtype != torch.float32 or net.dim() != 5:
+        raise L.RehrsegHipError("sr_volume_scatter: the network output is a 5-D float32 device tensor")
+    _chk_eval(img, torch.float32, "sr_volume_scatter img", 3)
+    _chk_mm(in_minmax, "sr_volume_scatter in_minmax")
+    _chk_mm(out_minmax, "sr_volume_scatter out_minmax")
+    b, Cc, n_out = net.shape[:3]
+    Zo, Y, X = img.shape
+    if Zo % n_out or net.shape[3] < X or net.shape[4] < Y or w0 < 0 or (int(w0) + b) * n_out > Zo:
+        raise L.RehrsegHipError(f"sr_volume_scatter: output {tuple(net.shape)} at window {w0} into {tuple(img.shape)}")
+    if seg is not None:
+        _chk_eval(seg, torch.uint8, "sr_volume_scatter seg", 3)
+        if tuple(seg.shape) != tuple(img.shape) or Cc < 2:
+            raise L.RehrsegHipError("sr_volume_scatter: seg has img's shape and needs a second channel")
+    strides = (C.c_int64 * 5)(*net.stride())
+    L.check(L.load().rehr_sr_volume_scatter_f32(_ptr(net), strides, b, Cc, n_out, X, Y, int(w0), Zo // n_out,
+                                                _ptr(in_minmax), _ptr(img), _ptr(seg), _ptr(out_minmax), _stream()),
+            "rehr_sr_volume_scatter_f32")
+
+
+def stage2_prep(img, minmax_codes, taps):
+    """zeroonenorm (min / max from the code pair) and the blur `taps` (float32 device vector, L <= 32) along the first
+    axis of img (X, ...) fp32, in one pass (rehr_stage2_prep_f32)."""
+    _chk_eval(img, torch.float32, "stage2_prep img")
+    _chk_eval(taps, torch.float32, "stage2_prep taps", 1)
+    _chk_mm(minmax_codes, "stage2_prep minmax")
+    if img.dim() < 2 or img.numel() == 0:
+        raise L.RehrsegHipError("stage2_prep: a non-empty image of at least two axes")
+    out = torch.empty_like(img)
+    X = img.shape[0]
+    L.check(L.load().rehr_stage2_prep_f32(_ptr(img), _ptr(minmax_codes), _ptr(taps), taps.numel(), _ptr(out), X,
+                                          img.numel() // X, _stream()), "rehr_stage2_prep_f32")
+    return out
+
+
+def stage2_unc_u8(u, minmax_codes):
+    """(zeroonenorm(u) * 255).astype('uint8') of the float32 device tensor u (rehr_stage2_unc_u8_f32)."""
+    _chk_eval(u, torch.float32, "stage2_unc_u8 input")
+    _chk_mm(minmax_codes, "stage2_unc_u8 minmax")
+    out = torch.empty(u.shape, device=u.device, dtype=torch.uint8)
+    L.check(L.load().rehr_stage2_unc_u8_f32(_ptr(u), _ptr(minmax_codes), _ptr(out), u.numel(), _stream()),
+            "rehr_stage2_unc_u8_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- sr_head.2 on the bf16 matrix cores
 def _thin5_ws(d, dev, f32=False):
     fn = L.load().rehr_conv5_thin_f32_workspace_bytes if f32 else L.load().rehr_conv5_thin_workspace_bytes

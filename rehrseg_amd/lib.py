@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("REHRSEG_HIP_LIB") or os.path.join(_HERE, "librehrseg_
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rehrseg_hip.h")
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
-ABI_VERSION = 4
+ABI_VERSION = 5
 GG_Y_F32 = 1            # rehr_gather_gemm_desc.flags
 GG_WS_READY = 2
 GG_WS_ONLY = 4
@@ -181,6 +181,11 @@ PROTOTYPES = {
     "rehr_tta_gather_f32": (C.c_int, [_vp, _vp] + [_i32] * 12 + [_vp]),
     "rehr_tta_blend_f16acc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "rehr_seg_eval_finalize_f16": (C.c_int, [_vp, _vp] + [_i32] * 9 + [_vp, _vp, _vp, _vp]),
+    "rehr_minmax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "rehr_sr_window_gather_f32": (C.c_int, [_vp, _vp] + [_i32] * 8 + [_vp]),
+    "rehr_sr_volume_scatter_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_vp, _vp, _vp, _vp, _vp]),
+    "rehr_stage2_prep_f32": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _vp]),
+    "rehr_stage2_unc_u8_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),

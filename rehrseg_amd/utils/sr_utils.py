@@ -3,8 +3,18 @@
 apply_to_vol_flavr (ref utils/sr_utils.py:102-135) slides a 4-slice window over the through-plane axis and
 calls the network once per window at batch 1.  The windows are independent, so here they are gathered on
 the device and pushed through the network in large batches (same kernels as training, far fewer launches,
-full CUs at 16-multiple slice sizes); the result tensor is identical in layout and values."""
+full CUs at 16-multiple slice sizes); the result tensor is identical in layout and values.
+
+The stage-1 -> stage-2 handoff (inference_flavr :137-242, zeroonenorm / postprocess_flavr :279-304; train_all.py:393-462)
+runs on the device as well: `sr_volume_flavr` feeds the windows straight out of the stored (x, y, z, 2) volume and
+scatters the network's output into the final volumes, `postprocess_flavr_volume` normalises and blurs them, and
+`stage2_volumes` returns what TrainSetMultipleSegSREfficient(volumes=...) consumes without leaving HBM.  The
+reference-named wrappers `inference_flavr` / `postprocess_flavr` take arrays and a dict where the reference takes file
+names (nibabel and SimpleITK are absent)."""
+import numpy as np
 import torch
+
+from .. import ops
 
 
 def _window_indices(S):
@@ -47,3 +57,150 @@ def apply_to_vol_flavr(model, image, pred_out_idx=None, window_batch=32):
     res = torch.cat(outs, 0)                                            # (n_windows, C_out, 4, Y, X)
     res = res.permute(0, 2, 1, 3, 4).reshape(-1, res.shape[1], ori_y, ori_x)
     return res.cpu()
+
+
+# ----------------------------------------------------------------------------- stage-1 -> stage-2 handoff on the device
+def _integral_separation(slice_separation):
+    sep = int(round(float(slice_separation)))
+    if sep < 1 or abs(float(slice_separation) - sep) > 1e-9:
+        # with an integral separation find_integer_p (utils/patch_ops.py:27-46) returns 0 at once (scale_tilde == 1):
+        # no reflect padding in front of the network and no crop behind it.  Only that case is built.
+        raise ValueError(f"slice_separation must be integral, got {slice_separation!r}")
+    return sep
+
+
+def _model_device(model):
+    return next(model.parameters()).device
+
+
+def _as_device_volume(volume, device):
+    if isinstance(volume, torch.Tensor):
+        return volume.to(device=device, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(volume, dtype=np.float32)).to(device)
+
+
+def sr_volume_flavr(model, volume, slice_separation, enable_uncertainty=False, window_batch=32):
+    """inference_flavr (ref :137-242) without files: `volume` is the merged (x, y, z, 2) array or device tensor (image,
+    label); returns device tensors in the layout the reference hands to SimpleITK, (4 (z - 1), y, x):
+
+      img          float32, the network's channel 0 after inv_normalize(., orig_min, orig_max, a=0, b=1)
+      seg          uint8, channel 1 after the same inv_normalize, > 0
+      uncertainty  float32 (enable_uncertainty), output 1 of the network after the same inv_normalize (:217-231; its two
+                   z_axis_to_lr_axis calls and the transpose(1, 2, 0, 3) cancel to the image's layout)
+      minmax       int32 [4]: min / max codes of img, then of uncertainty (hip_backend.minmax_decode reads them)
+
+    orig_min / orig_max span both channels of the input, as parse_image's (:73-74).  Gather, network and scatter run per
+    batch of `window_batch` windows in the caller's precision mode; nothing here reads device memory from the host."""
+    _integral_separation(slice_separation)
+    be = ops.get_backend()
+    dev = _model_device(model)
+    vol = _as_device_volume(volume, dev)
+    if vol.dim() != 4 or vol.shape[3] != 2:
+        raise ValueError(f"expected an (x, y, z, 2) volume, got {tuple(vol.shape)}")
+    X, Y, Z, _ = vol.shape
+    if Z < 2:
+        raise ValueError("sr_volume_flavr needs at least two slices")
+    n_windows, n_out = Z - 1, int(model.n_outputs)
+    in_mm = be.minmax(vol)
+    mm = be.minmax_new(dev, 2)
+    img = torch.empty((n_windows * n_out, Y, X), device=dev, dtype=torch.float32)
+    seg = torch.empty((n_windows * n_out, Y, X), device=dev, dtype=torch.uint8)
+    unc = torch.empty_like(img) if enable_uncertainty else None
+    with torch.inference_mode():
+        for w0 in range(0, n_windows, window_batch):
+            b = min(window_batch, n_windows - w0)
+            sr = model(be.sr_window_gather(vol, w0, b))
+            out, sigma = (sr[0], sr[1]) if isinstance(sr, tuple) else (sr, sr)   # pred_out_idx of a plain output: itself
+            be.sr_volume_scatter(out.float(), in_mm, w0, img, seg, mm[0:2])
+            if enable_uncertainty:
+                be.sr_volume_scatter(sigma.float(), in_mm, w0, unc, None, mm[2:4])
+    res = {"img": img, "seg": seg, "minmax": mm}
+    if enable_uncertainty:
+        res["uncertainty"] = unc
+    return res
+
+
+_taps_cache = {}   # (taps bytes, device) -> float32 device vector: a run blurs every subject with one profile
+
+
+def _device_taps(blur_kernel, device):
+    k = np.ascontiguousarray(np.asarray(blur_kernel, dtype=np.float32).reshape(-1))
+    key = (k.tobytes(), str(device))
+    if key not in _taps_cache:
+        _taps_cache[key] = torch.from_numpy(k).to(device)
+    return _taps_cache[key]
+
+
+def postprocess_flavr_volume(img, seg, blur_kernel, uncertainty=None, minmax=None):
+    """postprocess_flavr (ref :284-304) on the device.  img / seg / uncertainty are the volumes as sr_volume_flavr
+    returns them, (zo, y, x); the reference reads them back through nibabel as (x, y, zo), and that is the shape of all
+    three results (contiguous, as the data set wants them):
+
+      image        float32: zeroonenorm, then the blur `blur_kernel` (a parse_kernel result) along x, zero-padded 'same'
+      label        uint8 (the reference keeps nibabel's float32 of the same values)
+      uncertainty  uint8: zeros without a map (what train_all.py always gets: its `_uncertainty` path never exists), else
+                   (zeroonenorm(u) * 255).astype('uint8') -- values up to 65025 wrapped into 8 bits, as written
+
+    `minmax`: the code buffer of sr_volume_flavr (saves the two reductions); None computes them here."""
+    be = ops.get_backend()
+    xyz = lambda t: t.permute(2, 1, 0).contiguous()  # noqa: E731  SimpleITK array (z, y, x) -> nibabel (x, y, z)
+    image = xyz(img)
+    mm_img = minmax[0:2] if minmax is not None else be.minmax(image)
+    image = be.stage2_prep(image, mm_img, _device_taps(blur_kernel, img.device))
+    label = xyz(seg)
+    if uncertainty is None:
+        unc = torch.zeros_like(label)
+    else:
+        u = xyz(uncertainty)
+        unc = be.stage2_unc_u8(u, minmax[2:4] if minmax is not None else be.minmax(u))
+    return image, label, unc
+
+
+def stage2_volumes(model, volumes, slice_separation, blur_kernel, enable_uncertainty=False, window_batch=32):
+    """train_all.py:393-462 for a list of merged (x, y, z, 2) subjects: the {'img', 'seg', 'uncertainty'} dicts of
+    TrainSetMultipleSegSREfficient(volumes=...), resident on the model's device.  `window_batch` is sr_volume_flavr's:
+    the network's kernels pick their tiling by batch size, so two batchings agree to rounding, not bit for bit."""
+    res = []
+    for v in volumes:
+        r = sr_volume_flavr(model, v, slice_separation, enable_uncertainty, window_batch)
+        image, label, unc = postprocess_flavr_volume(r["img"], r["seg"], blur_kernel, r.get("uncertainty"), r["minmax"])
+        res.append({"img": image, "seg": label, "uncertainty": unc})
+    return res
+
+
+def _no_files(what):
+    if isinstance(what, (str, bytes)) or hasattr(what, "__fspath__"):
+        raise ImportError("reading or writing image files needs nibabel and SimpleITK, which are not installed; pass the "
+                          "merged (x, y, z, 2) volume as an array and a dict for the results instead")
+
+
+def inference_flavr(model, sr_mode, in_fpath, ref_fpath, out_fpath, slice_thickness, target_thickness, device,
+                    enable_uncertainty):
+    """The reference's signature (:137) with an (x, y, z, 2) array for `in_fpath` and a dict for `out_fpath`, which
+    receives '_img' / '_seg' ('img+seg') and '_uncertainty' (enable_uncertainty) as device tensors in the written
+    (zo, y, x) layout.  `ref_fpath` (spacing, origin, direction of the written files) is unused."""
+    for f in (in_fpath, out_fpath):
+        _no_files(f)
+    if sr_mode not in ("img+seg", "uncertainty"):
+        raise ValueError("sr_mode: 'img+seg' or 'uncertainty' (the reference's 'img' / 'seg' modes index a channel "
+                         "their one-channel result does not have)")
+    model = model.to(device)
+    r = sr_volume_flavr(model, in_fpath, float(slice_thickness / target_thickness), bool(enable_uncertainty))
+    if sr_mode == "img+seg":
+        out_fpath["_img"], out_fpath["_seg"] = r["img"], r["seg"]
+    if enable_uncertainty:
+        out_fpath["_uncertainty"] = r["uncertainty"]
+
+
+def postprocess_flavr(subject, slice_seperation=4, sr_path=None):
+    """The reference's signature (:284) with the dict inference_flavr filled for `sr_path`; the blur is the Gaussian of
+    parse_kernel at the FWHM parse_image derives from (slice_seperation, 1.0).  An '_uncertainty' entry is used when
+    present -- the reference looks for a file name that never exists and always returns zeros."""
+    _no_files(sr_path)
+    if sr_path is None:
+        _no_files("")
+    _integral_separation(slice_seperation)
+    from .blur_kernel_ops import parse_kernel
+    from .parse_image_file import blur_fwhm_voxels
+    kernel = parse_kernel(None, "gaussian", blur_fwhm_voxels(float(slice_seperation), 1.0))
+    return postprocess_flavr_volume(sr_path["_img"], sr_path["_seg"], kernel, sr_path.get("_uncertainty"))

@@ -328,7 +328,8 @@ class _DeviceSet(torch.utils.data.Dataset):
 # ----------------------------------------------------------------------------- stage 2: image / label / uncertainty patches
 class TrainSetMultipleSegSREfficient(_DeviceSet):
     """utils/train_set.py:21-160.  `volumes` (one dict per subject with 'img', 'seg' and, with `uncertainty`,
-    'uncertainty' arrays of shape (x, y, z)) replaces the H5 files when given.  `train_transform` stands where the
+    'uncertainty' arrays of shape (x, y, z), or tensors already on the data set's device, which stay there) replaces
+    the H5 files when given.  `train_transform` stands where the
     reference calls its batchgenerators chain (:64-84): "nnunet" builds that chain on the device (utils/augment.py;
     in-plane output `target_patch_size`), a callable over the keyword tensors data / seg / seg_sr / uncertainty is
     used as given, None (default) is the identity."""
@@ -355,6 +356,18 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
         if volumes is None:
             volumes = [_read_container(self._subject_file(image_path, s)) for s in split_subjects]
         for v in volumes:
+            if torch.is_tensor(v["img"]) and v["img"].device.type == self.device.type and \
+                    self.device.index in (None, v["img"].device.index):
+                # already in HBM (utils/sr_utils.py stage2_volumes): no host round trip, the same z-score on the device
+                img = v["img"].to(torch.float32)
+                if norm:
+                    img = img - img.mean()
+                    img = img / img.std(unbiased=False).clamp_min(1e-8)
+                self.imgs.append(img.contiguous())
+                self.labels.append(v["seg"].to(self.device, torch.uint8).contiguous())
+                self.uncertainties.append(v["uncertainty"].to(self.device, torch.uint8).contiguous()
+                                          if uncertainty else None)
+                continue
             img = np.asarray(v["img"])
             if norm:  # the reference normalises the whole volume on every access (:104-105): once is the same numbers
                 img = zscore_normalization(img.copy())
