@@ -23,6 +23,7 @@
 //    sum-of-squares that SEGating's pool and InstanceNorm3d need (double
 //    atomics, one per channel per wave).
 #include "common.h"
+#include "gg_shared.h"
 #include "halo_conv.h"
 #include "wino_conv.h"
 
@@ -31,13 +32,6 @@ namespace {
 constexpr int BK = 32;       // channels per K step
 constexpr int LDS_LD = 36;   // floats per LDS row (32 + 4 pad)
 constexpr int NTHREADS = 256;
-
-struct GGParams {
-  rehr_gather_gemm_desc d;
-  int tiles_d, tiles_h, tiles_w, m_tiles, n_tiles;
-  int kchunks;  // Cin / 32
-  int64_t wp_bytes;
-};
 
 // LDSBUF = 2: double-buffered LDS tiles, one barrier per K step (register-heavy 128x128 tile,
 //             2 blocks per CU anyway).
@@ -339,31 +333,7 @@ __device__ __forceinline__ void gather_gemm_body(const GGParams& p, const int nb
   }
 }
 
-constexpr int MAX_PHASES = 8;
-// Several launches that differ only in lattice / taps / destination offset (the stride
-// phases of one transposed conv or strided input gradient) share ONE grid: blockIdx.z picks
-// the phase, so four quarter-size launches fill the chip like one full-size launch.
-// interleave != 0 (REHR_DBG_GG_INTERLEAVE; all phases have the same tile counts -- kernel = stride transposed
-// convolutions, input gradients of strided convolutions on even extents): a 1-D grid in which the `count` phases of one
-// lattice tile are CONSECUTIVE blocks of ONE XCD, so that the tile's source rows come from HBM once and from that XCD's L2
-// for the other phases (with blockIdx.z = phase the source tensor is streamed once per phase).  Tried in round 3 and
-// measured SLOWER in the step (cfg-3 +1.4 ms, cfg-5 +0.25 ms, profiles/r03_ab_phase_interleave.txt): these launches are
-// bound by block turnover (K = C_in only: two k-steps per block), not by the source re-reads, and eight blocks storing
-// into the same 2x2x2 output neighbourhood at once serialise at the memory side.  Off by default; tests keep it alive.
-struct GGMulti {
-  GGParams ph[MAX_PHASES];
-  int interleave, count, no_interleave;
-};
-
-// block b of the interleaved grid -> (phase, logical tile); false: padding block
-__device__ __forceinline__ bool interleaved_block(int b, int m_tiles, int n_tiles, int count, int& phase, int& logical) {
-  const int xcd = b & 7, j = b >> 3, per = count * n_tiles;
-  const int mt = (j / per) * 8 + xcd, rem = j % per;
-  phase = rem / n_tiles;
-  logical = mt * n_tiles + (rem - phase * n_tiles);
-  return mt < m_tiles;
-}
-
+// GGMulti (gg_shared.h): the phases of one layer in one grid, blockIdx.z = phase or the interleaved 1-D grid
 template <int BM, int BN, int WGM, int WGN, int LDSBUF>
 __global__ __launch_bounds__(NTHREADS, (LDSBUF == 1 ? 3 : 2)) void gather_gemm_multi_kernel(const GGMulti pm) {
   int phase, logical;
@@ -390,93 +360,12 @@ __global__ __launch_bounds__(NTHREADS, (LDSBUF == 1 ? 3 : 2)) void gather_gemm_k
 
 template <int BM, int BN, int WGM, int WGN, int LDSBUF>
 int launch_gg(const GGMulti& pm, int count, hipStream_t stream) {
-  const size_t smem = (size_t)LDSBUF * (BM + BN) * LDS_LD * sizeof(float) + BM * sizeof(int);
-  static bool attr_set = false;
-  auto kern1 = gather_gemm_kernel<BM, BN, WGM, WGN, LDSBUF>;
-  auto kernm = gather_gemm_multi_kernel<BM, BN, WGM, WGN, LDSBUF>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern1), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
-  if (count == 1) {
-    const GGParams& p = pm.ph[0];
-    hipLaunchKernelGGL(kern1, dim3(p.m_tiles * p.n_tiles, p.d.N, 1), dim3(NTHREADS), smem, stream, p);
-  } else {
-    int nb = 0;
-    bool uniform = true;
-    for (int i = 0; i < count; ++i) {
-      const int n = pm.ph[i].m_tiles * pm.ph[i].n_tiles;
-      nb = n > nb ? n : nb;
-      uniform = uniform && pm.ph[i].m_tiles == pm.ph[0].m_tiles && pm.ph[i].n_tiles == pm.ph[0].n_tiles;
-    }
-    GGMulti pmi = pm;
-    pmi.count = count;
-    const int64_t gx = (int64_t)((pm.ph[0].m_tiles + 7) / 8) * 8 * count * pm.ph[0].n_tiles;
-    pmi.interleave = (uniform && !pm.no_interleave && gx < (1ll << 31)) ? 1 : 0;
-    if (pmi.interleave) hipLaunchKernelGGL(kernm, dim3((unsigned)gx, pm.ph[0].d.N, 1), dim3(NTHREADS), smem, stream, pmi);
-    else hipLaunchKernelGGL(kernm, dim3(nb, pm.ph[0].d.N, count), dim3(NTHREADS), smem, stream, pmi);
-  }
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  constexpr size_t smem = (size_t)LDSBUF * (BM + BN) * LDS_LD * sizeof(float) + BM * sizeof(int);
+  return gg_launch<gather_gemm_kernel<BM, BN, WGM, WGN, LDSBUF>, gather_gemm_multi_kernel<BM, BN, WGM, WGN, LDSBUF>,
+                   NTHREADS, smem>(pm, count, stream);
 }
 
-bool taps_ok(const rehr_axis_taps& t) { return t.count >= 1; }
-
-int validate(const rehr_gather_gemm_desc& d) {
-  if (!d.x1 || !d.wp || !d.y) return REHR_EINVAL;
-  if (d.N < 1 || d.Cin < 16 || d.Cin % 16 || d.c1 < 0 || d.c1 > d.Cin) return REHR_EINVAL;
-  if (d.c1 < d.Cin && d.c1 % 32) return REHR_EINVAL;  // a virtual concat splits on a chunk boundary
-  if (d.c1 < d.Cin && !d.x2) return REHR_EINVAL;
-  if (d.c1 == 0) return REHR_EINVAL;
-  if (d.ldx1 % 4 || (d.x2 && d.ldx2 % 4)) return REHR_EINVAL;
-  if (((uintptr_t)d.x1 | (uintptr_t)d.wp | (uintptr_t)(d.x2 ? d.x2 : d.x1)) & 15) return REHR_EINVAL;
-  if (d.Npad % 32 || d.Npad < d.Cout || d.Cout < 1) return REHR_EINVAL;
-  if (d.Ld < 1 || d.Lh < 1 || d.Lw < 1) return REHR_EINVAL;
-  if (!taps_ok(d.td) || !taps_ok(d.th) || !taps_ok(d.tw)) return REHR_EINVAL;
-  if (d.tile_d != 0 &&
-      (d.tile_d < 1 || d.tile_h < 1 || d.tile_w < 1 || d.tile_d * d.tile_h * d.tile_w != 128))
-    return REHR_EINVAL;
-  if (d.stats_mode != 0 && !d.stats) return REHR_EINVAL;
-  if (d.N > 65535) return REHR_EINVAL;
-  // destination extent check: the last lattice point must land inside y
-  const int64_t yd = (int64_t)(d.Ld - 1) * d.osd + d.obd, yh = (int64_t)(d.Lh - 1) * d.osh + d.obh,
-                yw = (int64_t)(d.Lw - 1) * d.osw + d.obw;
-  if (d.obd < 0 || d.obh < 0 || d.obw < 0 || yd >= d.Dy || yh >= d.Hy || yw >= d.Wy) return REHR_EINVAL;
-  if (d.ldy < d.Cout) return REHR_EINVAL;
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return REHR_EINVAL;
-  return REHR_OK;
-}
-
-int plan(const rehr_gather_gemm_desc& d, GGParams& p) {
-  p.d = d;
-  if (d.tile_d == 0) {
-    p.tiles_d = p.tiles_h = 1;
-    p.tiles_w = (int)(((int64_t)d.Ld * d.Lh * d.Lw + 127) / 128);
-    p.m_tiles = p.tiles_w;
-  } else {
-    p.tiles_d = (d.Ld + d.tile_d - 1) / d.tile_d;
-    p.tiles_h = (d.Lh + d.tile_h - 1) / d.tile_h;
-    p.tiles_w = (d.Lw + d.tile_w - 1) / d.tile_w;
-    p.m_tiles = p.tiles_d * p.tiles_h * p.tiles_w;
-  }
-  p.kchunks = (d.Cin + 31) / 32;
-  // buffer-addressed operands: 32-bit byte offsets per sample / per weight panel
-  const int64_t kd_max = d.td.k0 + (int64_t)d.td.ks * (d.td.count - 1);
-  const int64_t kh_max = d.th.k0 + (int64_t)d.th.ks * (d.th.count - 1);
-  const int64_t kw_max = d.tw.k0 + (int64_t)d.tw.ks * (d.tw.count - 1);
-  const int64_t taps_all = ((kd_max * d.KH) + kh_max) * d.KW + kw_max + 1;
-  p.wp_bytes = taps_all * d.Npad * d.Cin * 4;
-  const int64_t img = (int64_t)d.Di * d.Hi * d.Wi * 4;
-  if (p.wp_bytes >= (1ll << 32) - 64 || img * d.ldx1 >= (1ll << 32) - 64 ||
-      (d.x2 && img * d.ldx2 >= (1ll << 32) - 64))
-    return REHR_ENOSUP;
-  p.n_tiles = d.Npad / (d.Npad % 128 == 0 ? 128 : (d.Npad % 64 == 0 ? 64 : 32));
-  return REHR_OK;
-}
+int validate(const rehr_gather_gemm_desc& d) { return gg_validate(d, 4); }
 
 int launch_generic(const GGMulti& pm, int count, hipStream_t st) {
   const int npad = pm.ph[0].d.Npad;
@@ -496,6 +385,7 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
     if (descs[i].Npad != descs[0].Npad || descs[i].N != descs[0].N || descs[i].wp != descs[0].wp ||
         descs[i].x1 != descs[0].x1)
       return REHR_EINVAL;  // (y may differ: split-K partials go to separate slabs)
+    // (Cin and c1 may differ as well, unlike in rehr_gather_gemm_multi_bf16: the K step is 32 channels for every phase)
   }
   hipStream_t st = (hipStream_t)stream;
   // REHR_GG_WS_ONLY: the weight transforms of this call and nothing else (every Winograd try-function below returns
@@ -540,7 +430,7 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
       if (hrc == REHR_OK) continue;
       if (hrc != REHR_ENOSUP) return hrc;
     }
-    const int rc = plan(descs[i], pm.ph[n]);
+    const int rc = gg_plan(descs[i], pm.ph[n], 4, BK);
     if (rc != REHR_OK) return rc;
     ++n;
   }

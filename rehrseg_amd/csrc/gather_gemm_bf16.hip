@@ -18,6 +18,7 @@
 //  * register-staged pipeline two K steps ahead, branch-free raw buffer loads (out-of-range = zero padding), as
 //    in the fp32 kernel.
 #include "common.h"
+#include "gg_shared.h"
 #include "wino_conv.h"
 
 int halo_conv_bf16_try(const rehr_gather_gemm_desc& d, hipStream_t stream);  // halo_conv_bf16.hip
@@ -30,15 +31,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int NTHREADS = 256;
 constexpr int ES = 2;  // bytes per element
 
-struct GBParams {
-  rehr_gather_gemm_desc d;
-  int tiles_d, tiles_h, tiles_w, m_tiles, n_tiles;
-  int kchunks;
-  int64_t wp_bytes;
-};
-
 template <int BM, int BN, int WGM, int WGN, int LDSBUF, int BK>
-__device__ __forceinline__ void gg_bf16_body(const GBParams& p, const int nblocks, const int logical_in = -1) {
+__device__ __forceinline__ void gg_bf16_body(const GGParams& p, const int nblocks, const int logical_in = -1) {
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
   constexpr int FM = WTM / 32, FN = WTN / 32;
   constexpr int TPR = BK / 8;                 // threads per row (16 bytes = 8 channels each)
@@ -319,26 +313,12 @@ __device__ __forceinline__ void gg_bf16_body(const GBParams& p, const int nblock
   }
 }
 
-constexpr int MAX_PHASES = 8;
-// interleave: see GGMulti in gather_gemm.hip -- the phases of one lattice tile as consecutive blocks of one XCD
-struct GBMulti {
-  GBParams ph[MAX_PHASES];
-  int interleave, count, no_interleave;
-};
-
-__device__ __forceinline__ bool interleaved_block_b(int b, int m_tiles, int n_tiles, int count, int& phase, int& logical) {
-  const int xcd = b & 7, j = b >> 3, per = count * n_tiles;
-  const int mt = (j / per) * 8 + xcd, rem = j % per;
-  phase = rem / n_tiles;
-  logical = mt * n_tiles + (rem - phase * n_tiles);
-  return mt < m_tiles;
-}
-
+// GGMulti (gg_shared.h): the phases of one layer in one grid, blockIdx.z = phase or the interleaved 1-D grid
 template <int BM, int BN, int WGM, int WGN, int LDSBUF, int BK>
-__global__ __launch_bounds__(NTHREADS, 2) void gather_gemm_bf16_multi_kernel(const GBMulti pm) {
+__global__ __launch_bounds__(NTHREADS, 2) void gather_gemm_bf16_multi_kernel(const GGMulti pm) {
   int phase, logical;
   if (pm.interleave) {
-    if (!interleaved_block_b((int)blockIdx.x, pm.ph[0].m_tiles, pm.ph[0].n_tiles, pm.count, phase, logical)) return;
+    if (!interleaved_block((int)blockIdx.x, pm.ph[0].m_tiles, pm.ph[0].n_tiles, pm.count, phase, logical)) return;
   } else {
     phase = blockIdx.z;
     const int nb = pm.ph[phase].m_tiles * pm.ph[phase].n_tiles;
@@ -350,97 +330,23 @@ __global__ __launch_bounds__(NTHREADS, 2) void gather_gemm_bf16_multi_kernel(con
   gg_bf16_body<BM, BN, WGM, WGN, LDSBUF, BK>(pm.ph[phase], 0, logical);
 }
 template <int BM, int BN, int WGM, int WGN, int LDSBUF, int BK>
-__global__ __launch_bounds__(NTHREADS, 2) void gather_gemm_bf16_kernel(const GBParams p) {
+__global__ __launch_bounds__(NTHREADS, 2) void gather_gemm_bf16_kernel(const GGParams p) {
   gg_bf16_body<BM, BN, WGM, WGN, LDSBUF, BK>(p, (int)gridDim.x);
 }
 
 template <int BM, int BN, int WGM, int WGN, int LDSBUF, int BK>
-int launch_gb(const GBMulti& pm, int count, hipStream_t stream) {
-  const size_t smem = (size_t)LDSBUF * (BM + BN) * (BK * ES + 16) + BM * sizeof(int);
-  static bool attr_set = false;
-  auto kern1 = gather_gemm_bf16_kernel<BM, BN, WGM, WGN, LDSBUF, BK>;
-  auto kernm = gather_gemm_bf16_multi_kernel<BM, BN, WGM, WGN, LDSBUF, BK>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern1), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
-  if (count == 1) {
-    const GBParams& p = pm.ph[0];
-    hipLaunchKernelGGL(kern1, dim3(p.m_tiles * p.n_tiles, p.d.N, 1), dim3(NTHREADS), smem, stream, p);
-  } else {
-    int nb = 0;
-    bool uniform = true;
-    for (int i = 0; i < count; ++i) {
-      const int n = pm.ph[i].m_tiles * pm.ph[i].n_tiles;
-      nb = n > nb ? n : nb;
-      uniform = uniform && pm.ph[i].m_tiles == pm.ph[0].m_tiles && pm.ph[i].n_tiles == pm.ph[0].n_tiles;
-    }
-    GBMulti pmi = pm;
-    pmi.count = count;
-    const int64_t gx = (int64_t)((pm.ph[0].m_tiles + 7) / 8) * 8 * count * pm.ph[0].n_tiles;
-    pmi.interleave = (uniform && !pm.no_interleave && gx < (1ll << 31)) ? 1 : 0;
-    if (pmi.interleave) hipLaunchKernelGGL(kernm, dim3((unsigned)gx, pm.ph[0].d.N, 1), dim3(NTHREADS), smem, stream, pmi);
-    else hipLaunchKernelGGL(kernm, dim3(nb, pm.ph[0].d.N, count), dim3(NTHREADS), smem, stream, pmi);
-  }
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+int launch_gb(const GGMulti& pm, int count, hipStream_t stream) {
+  constexpr size_t smem = (size_t)LDSBUF * (BM + BN) * (BK * ES + 16) + BM * sizeof(int);
+  return gg_launch<gather_gemm_bf16_kernel<BM, BN, WGM, WGN, LDSBUF, BK>,
+                   gather_gemm_bf16_multi_kernel<BM, BN, WGM, WGN, LDSBUF, BK>, NTHREADS, smem>(pm, count, stream);
 }
 
-int validate(const rehr_gather_gemm_desc& d) {
-  if (!d.x1 || !d.wp || !d.y) return REHR_EINVAL;
-  if (d.N < 1 || d.Cin < 16 || d.Cin % 16 || d.c1 < 1 || d.c1 > d.Cin) return REHR_EINVAL;
-  if (d.c1 < d.Cin && (d.c1 % 32 || !d.x2)) return REHR_EINVAL;  // a virtual concat splits on a chunk boundary
-  if (d.ldx1 % 8 || (d.x2 && d.ldx2 % 8)) return REHR_EINVAL;    // 16-byte rows
-  if (((uintptr_t)d.x1 | (uintptr_t)d.wp | (uintptr_t)(d.x2 ? d.x2 : d.x1)) & 15) return REHR_EINVAL;
-  if (d.Npad % 32 || d.Npad < d.Cout || d.Cout < 1) return REHR_EINVAL;
-  if (d.Ld < 1 || d.Lh < 1 || d.Lw < 1) return REHR_EINVAL;
-  if (d.td.count < 1 || d.th.count < 1 || d.tw.count < 1) return REHR_EINVAL;
-  if (d.tile_d != 0 && (d.tile_d < 1 || d.tile_h < 1 || d.tile_w < 1 || d.tile_d * d.tile_h * d.tile_w != 128))
-    return REHR_EINVAL;
-  if (d.stats_mode != 0 && !d.stats) return REHR_EINVAL;
-  if (d.N > 65535) return REHR_EINVAL;
-  const int64_t yd = (int64_t)(d.Ld - 1) * d.osd + d.obd, yh = (int64_t)(d.Lh - 1) * d.osh + d.obh,
-                yw = (int64_t)(d.Lw - 1) * d.osw + d.obw;
-  if (d.obd < 0 || d.obh < 0 || d.obw < 0 || yd >= d.Dy || yh >= d.Hy || yw >= d.Wy) return REHR_EINVAL;
-  if (d.ldy < d.Cout) return REHR_EINVAL;
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return REHR_EINVAL;
-  return REHR_OK;
-}
+int validate(const rehr_gather_gemm_desc& d) { return gg_validate(d, ES); }
 
+// 64-channel K steps when neither Cin nor the concat split leaves a half chunk
 bool chunk64(const rehr_gather_gemm_desc& d) { return d.Cin % 64 == 0 && (d.c1 == d.Cin || d.c1 % 64 == 0); }
 
-int plan(const rehr_gather_gemm_desc& d, GBParams& p) {
-  p.d = d;
-  if (d.tile_d == 0) {
-    p.tiles_d = p.tiles_h = 1;
-    p.tiles_w = (int)(((int64_t)d.Ld * d.Lh * d.Lw + 127) / 128);
-    p.m_tiles = p.tiles_w;
-  } else {
-    p.tiles_d = (d.Ld + d.tile_d - 1) / d.tile_d;
-    p.tiles_h = (d.Lh + d.tile_h - 1) / d.tile_h;
-    p.tiles_w = (d.Lw + d.tile_w - 1) / d.tile_w;
-    p.m_tiles = p.tiles_d * p.tiles_h * p.tiles_w;
-  }
-  const int bk = chunk64(d) ? 64 : 32;
-  p.kchunks = (d.Cin + bk - 1) / bk;
-  const int64_t kd_max = d.td.k0 + (int64_t)d.td.ks * (d.td.count - 1);
-  const int64_t kh_max = d.th.k0 + (int64_t)d.th.ks * (d.th.count - 1);
-  const int64_t kw_max = d.tw.k0 + (int64_t)d.tw.ks * (d.tw.count - 1);
-  const int64_t taps_all = ((kd_max * d.KH) + kh_max) * d.KW + kw_max + 1;
-  p.wp_bytes = taps_all * d.Npad * d.Cin * ES;
-  const int64_t img = (int64_t)d.Di * d.Hi * d.Wi * ES;
-  if (p.wp_bytes >= (1ll << 32) - 64 || img * d.ldx1 >= (1ll << 32) - 64 ||
-      (d.x2 && img * d.ldx2 >= (1ll << 32) - 64))
-    return REHR_ENOSUP;
-  p.n_tiles = d.Npad / (d.Npad % 128 == 0 ? 128 : (d.Npad % 64 == 0 ? 64 : 32));
-  return REHR_OK;
-}
-
-int launch_generic(const GBMulti& pm, int count, hipStream_t st) {
+int launch_generic(const GGMulti& pm, int count, hipStream_t st) {
   const int npad = pm.ph[0].d.Npad;
   const bool k64 = chunk64(pm.ph[0].d);
   if (npad % 128 == 0)
@@ -477,7 +383,7 @@ extern "C" int rehr_gather_gemm_multi_bf16(const rehr_gather_gemm_desc* descs, i
       if (trc != REHR_ENOSUP) return trc;
     }
   }
-  GBMulti pm;
+  GGMulti pm;
   pm.interleave = 0;
   pm.count = 0;
   pm.no_interleave = (descs[0].debug_flags & REHR_DBG_GG_INTERLEAVE) ? 0 : 1;
@@ -487,7 +393,7 @@ extern "C" int rehr_gather_gemm_multi_bf16(const rehr_gather_gemm_desc* descs, i
     if (rc != REHR_OK) return rc;
     if (descs[i].Npad != descs[0].Npad || descs[i].N != descs[0].N || descs[i].wp != descs[0].wp ||
         descs[i].x1 != descs[0].x1 || descs[i].Cin != descs[0].Cin || descs[i].c1 != descs[0].c1)
-      return REHR_EINVAL;
+      return REHR_EINVAL;   // (Cin, c1: stricter than rehr_gather_gemm_multi_f32 -- launch_generic takes chunk64() from phase 0)
     // (tap-range parts of a split-K launch -- they differ in y -- stay together in ONE generic grid: a halo launch per
     // part would run them one after the other on a few CUs each)
     const bool split_part = count > 1 && descs[i].y != descs[(i + 1) % count].y;
@@ -496,7 +402,7 @@ extern "C" int rehr_gather_gemm_multi_bf16(const rehr_gather_gemm_desc* descs, i
       if (rc == REHR_OK) continue;
       if (rc != REHR_ENOSUP) return rc;
     }
-    rc = plan(descs[i], pm.ph[n]);
+    rc = gg_plan(descs[i], pm.ph[n], ES, chunk64(descs[i]) ? 64 : 32);
     if (rc != REHR_OK) return rc;
     ++n;
   }
@@ -513,6 +419,9 @@ extern "C" int rehr_pack_weights_bf16(const float* in, void* out, int32_t A, int
                                       int32_t transpose_ab, void* stream) {
   if (!in || !out || A < 1 || Apad < A || B < 1 || T < 1) return REHR_EINVAL;
   const int64_t total = (int64_t)T * Apad * B;
+  // (grid sized by hand: ew_blocks(), which rehr_pack_weights_f32 uses, is local to elementwise.hip.  Today both give
+  // 256 threads and at most 2048 blocks, and they differ only in ew_blocks() raising 0 blocks to 1, which total >= 1
+  // rules out here; the kernel is a grid-stride loop, so the two need not be kept in step)
   int64_t blocks = (total + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in,

@@ -11,6 +11,7 @@
 // range of tiles and fetch the next (tile, chunk) halo into registers during the current
 // sweep, so HBM/L2 latency hides behind ~28k-55k cycles of MFMA work.
 #include "common.h"
+#include "gg_shared.h"
 #include "halo_conv.h"
 
 namespace {
@@ -251,17 +252,6 @@ __global__ __launch_bounds__(256, 2) void halo_conv_kernel(const HaloParams p) {
   }
 }
 
-void span(const rehr_axis_taps& t, int b, int* mn, int* mx) {
-  int lo = b + t.off0, hi = lo;
-  for (int j = 1; j < t.count; ++j) {
-    const int o = b + t.off0 + t.offs * j;
-    if (o < lo) lo = o;
-    if (o > hi) hi = o;
-  }
-  *mn = lo;
-  *mx = hi;
-}
-
 template <int BN, int WGM, int WGN>
 int launch(const HaloParams& p, size_t smem, hipStream_t stream) {
   auto kern = halo_conv_kernel<BN, WGM, WGN>;
@@ -301,22 +291,16 @@ int halo_conv_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
   if (p.hvox > MAXX * 32 || p.HH > 1023 || p.HW > 1023) return REHR_ENOSUP;
   const size_t smem = (size_t)p.hvox * LDX * sizeof(float) + BVOX * sizeof(int);
   if (smem > 80 * 1024) return REHR_ENOSUP;
-  const int64_t img = (int64_t)d.Di * d.Hi * d.Wi * 4;
-  if (img * d.ldx1 >= (1ll << 32) - 64 || (d.x2 && img * d.ldx2 >= (1ll << 32) - 64)) return REHR_ENOSUP;
+  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return REHR_ENOSUP;
   if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return REHR_ENOSUP;
   p.mind = mn[0]; p.minh = mn[1]; p.minw = mn[2];
   p.nb_d = (int)nb_d; p.nb_h = (int)nb_h; p.nb_w = (int)nb_w;
   p.tiles_per_img = (int)(nb_d * nb_h * nb_w);
   p.ntiles = (int64_t)d.N * p.tiles_per_img;
   p.kchunks = (d.Cin + 31) / 32;
-  {
-    const int64_t kd_max = d.td.k0 + (int64_t)d.td.ks * (d.td.count - 1);
-    const int64_t kh_max = d.th.k0 + (int64_t)d.th.ks * (d.th.count - 1);
-    const int64_t kw_max = d.tw.k0 + (int64_t)d.tw.ks * (d.tw.count - 1);
-    const int64_t wb = (((kd_max * d.KH) + kh_max) * d.KW + kw_max + 1) * d.Npad * d.Cin * 4;
-    if (wb >= (1ll << 32) - 64) return REHR_ENOSUP;
-    p.wp_bytes = (uint32_t)wb;
-  }
+  const int64_t wb = gg_wp_bytes(d, 4);
+  if (wb >= GG_BUF_LIMIT) return REHR_ENOSUP;
+  p.wp_bytes = (uint32_t)wb;
   // persistent blocks: 512 resident (256 CUs x 2); full rounds, >= 2 tiles each when possible
   const int n_tiles = d.Npad / (d.Npad % 64 == 0 ? 64 : 32);
   int64_t want = 1024 / n_tiles;

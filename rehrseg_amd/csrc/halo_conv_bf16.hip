@@ -23,6 +23,7 @@
 // Epilogue semantics as in the gather kernel: bias, ReLU / LeakyReLU, bf16 (or fp32) store, fp64 statistics formed
 // from the fp32 values.
 #include "common.h"
+#include "gg_shared.h"
 
 namespace {
 
@@ -451,17 +452,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void halo_conv_bf16_kernel(const HBPar
   if (want_stats && stats_n >= 0) flush_stats(stats_n);
 }
 
-void span(const rehr_axis_taps& t, int b, int* mn, int* mx) {
-  int lo = b + t.off0, hi = lo;
-  for (int j = 1; j < t.count; ++j) {
-    const int o = b + t.off0 + t.offs * j;
-    if (o < lo) lo = o;
-    if (o > hi) hi = o;
-  }
-  *mn = lo;
-  *mx = hi;
-}
-
 template <int BD, int BH, int BW, int NT3, int NWV>
 int launch(HBParams p, hipStream_t stream) {
   constexpr int RPP = HBW<NWV>::RPP;
@@ -519,18 +509,12 @@ int halo_conv_bf16_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
   p.d = d;
   p.HD = mx[0] - mn[0]; p.HH = mx[1] - mn[1]; p.HW = mx[2] - mn[2];   // halo extents, completed per brick in launch()
   p.mind = mn[0]; p.minh = mn[1]; p.minw = mn[2];
-  const int64_t img = (int64_t)d.Di * d.Hi * d.Wi * 2;
-  if (img * d.ldx1 >= (1ll << 32) - 64 || (d.x2 && img * d.ldx2 >= (1ll << 32) - 64)) return REHR_ENOSUP;
+  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 2)) return REHR_ENOSUP;
   if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return REHR_ENOSUP;
   p.kchunks = (d.Cin + BK - 1) / BK;
-  {
-    const int64_t kd_max = d.td.k0 + (int64_t)d.td.ks * (d.td.count - 1);
-    const int64_t kh_max = d.th.k0 + (int64_t)d.th.ks * (d.th.count - 1);
-    const int64_t kw_max = d.tw.k0 + (int64_t)d.tw.ks * (d.tw.count - 1);
-    const int64_t wb = (((kd_max * d.KH) + kh_max) * d.KW + kw_max + 1) * d.Npad * d.Cin * 2;
-    if (wb >= (1ll << 32) - 64) return REHR_ENOSUP;
-    p.wp_bytes = (uint32_t)wb;
-  }
+  const int64_t wb = gg_wp_bytes(d, 2);
+  if (wb >= GG_BUF_LIMIT) return REHR_ENOSUP;
+  p.wp_bytes = (uint32_t)wb;
   // brick shapes in order of preference; one that pads the lattice by more than 1.3x (or does not fit it) declines
   // (eight waves per block, two per SIMD; the four-wave organisation of round 2's first half was 1.0 ms per step slower
   // on the bf16 cfg-3 step: profiles/r03_ab_superseded.txt)

@@ -17,6 +17,7 @@
 //   schedule = three waves per SIMD hide each other's LDS latency; weights one k-group ahead in
 //              registers, next patch fetched at the top of an item, one barrier per item
 #include "common.h"
+#include "gg_shared.h"
 #include "wino_conv.h"
 #include "wino22_shared.h"
 #include <cstdlib>
@@ -712,8 +713,7 @@ bool plan22_flat(const rehr_gather_gemm_desc& d, F22Params& p, int parts = 1) {
   const int64_t need = (int64_t)p.nphase * d.td.count * 9 * d.Npad * p.kchunks * 32 * 4;
   if (need >= (1ll << 32) - 64) return false;
   p.up_bytes = (uint32_t)need;
-  const int64_t tot = (int64_t)d.N * d.Di * d.Hi * d.Wi * 4;
-  if (tot * d.ldx1 >= (1ll << 32) - 64 || (d.x2 && tot * d.ldx2 >= (1ll << 32) - 64)) return false;
+  if (!gg_src_fits(d, (int64_t)d.N * d.Di * d.Hi * d.Wi, 4)) return false;   // one buffer over the whole batch
   if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31) || d.Npad / 64 > 65535) return false;
   const int64_t xfl = (int64_t)2 * (p.rows * p.RP + LD + 4), efl = (int64_t)4 * 3 * 2 * 16 * 64;
   const int64_t rfl = (int64_t)F22_MAXSLOT * 12 * 2 * 2 * 32;
@@ -754,8 +754,7 @@ bool plan22(const rehr_gather_gemm_desc& d, W22Params& p) {
   const int64_t need = (int64_t)p.nphase * d.td.count * 9 * d.Npad * p.kchunks * 32 * 4;
   if (need >= (1ll << 32) - 64) return false;
   p.up_bytes = (uint32_t)need;
-  const int64_t img = (int64_t)d.Di * d.Hi * d.Wi * 4;
-  if (img * d.ldx1 >= (1ll << 32) - 64 || (d.x2 && img * d.ldx2 >= (1ll << 32) - 64)) return false;
+  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return false;
   if ((int64_t)p.nb_h * p.nb_w * d.Ld >= (1ll << 31) || d.Npad / 64 > 65535 || d.N > 65535) return false;
   return true;
 }

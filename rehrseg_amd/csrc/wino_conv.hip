@@ -15,6 +15,7 @@
 //             column ahead.
 //   output  = Y = A^T M A: column combine in registers, row combine across the 4 waves via LDS.
 #include "common.h"
+#include "gg_shared.h"
 #include "wino_conv.h"
 #include <cstdlib>
 
@@ -1005,12 +1006,6 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wino_conv_w32p_kernel
   }
 }
 
-bool three_taps(const rehr_axis_taps& t, int b) {
-  if (t.count != 3) return false;
-  const int o0 = b + t.off0, o1 = b + t.off0 + t.offs, o2 = b + t.off0 + 2 * t.offs;
-  return (o1 == 0) && ((o0 == -1 && o2 == 1) || (o0 == 1 && o2 == -1));
-}
-
 bool w32_ok(const rehr_gather_gemm_desc& d) {
   if (d.Npad % 64 == 0 || d.Lh < 16 || d.Lw < 16) return false;  // 64-multiples: the big-tile kernel is faster
   const int64_t nb_h = (d.Lh + 15) / 16, nb_w = (d.Lw + 15) / 16;
@@ -1073,8 +1068,7 @@ int64_t wino_workspace_bytes(const rehr_gather_gemm_desc& d) {
   const int64_t cpad = (int64_t)((d.Cin + 31) / 32) * 32;  // the fragment-order layout pads Cin to 32
   const int64_t need = (int64_t)d.td.count * 16 * d.Npad * cpad * (int64_t)sizeof(float);
   if (need >= (1ll << 32) - 64) return 0;
-  const int64_t img = (int64_t)d.Di * d.Hi * d.Wi * 4;
-  if (img * d.ldx1 >= (1ll << 32) - 64 || (d.x2 && img * d.ldx2 >= (1ll << 32) - 64)) return 0;
+  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return 0;
   if (nb_h * nb_w * d.Ld >= (1ll << 31) || d.Npad / 32 > 65535 || d.N > 65535) return 0;
   return need;
 }

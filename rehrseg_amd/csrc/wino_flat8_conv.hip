@@ -13,6 +13,7 @@
 // NFM = 2: 512 threads, one block per CU (two waves per SIMD).  NFM = 1: 256 threads, two independent blocks per CU
 // -- half the tiles per block, for layers whose 64-tile block count quantises badly on 256 CUs.
 #include "common.h"
+#include "gg_shared.h"
 #include "wino_conv.h"
 
 namespace {
@@ -365,12 +366,6 @@ __global__ __launch_bounds__(256 * NFM, NFM == 1 ? 2 : 1) void wino_flat8_conv_k
   }
 }
 
-bool three_taps_f8(const rehr_axis_taps& t, int b) {
-  if (t.count != 3) return false;
-  const int o0 = b + t.off0, o1 = b + t.off0 + t.offs, o2 = b + t.off0 + 2 * t.offs;
-  return (o1 == 0) && ((o0 == -1 && o2 == 1) || (o0 == 1 && o2 == -1));
-}
-
 // LDS bank-group spread of one 16-lane phase of a fragment read: lanes = 16 consecutive tiles at one column parity,
 // 16-byte units (tw * 9 + (row pitch / 2) * tile row) mod 16; returns the worst multiplicity over the alignments
 int f8_conflicts(int ntw, int RP) {
@@ -391,7 +386,7 @@ bool plan_flat8(const rehr_gather_gemm_desc& d, Flat8Params& p, int nfm) {
   if (d.osd != 1 || d.osh != 1 || d.osw != 1 || d.obd || d.obh || d.obw) return false;
   if (d.Ld != d.Dy || d.Lh != d.Hy || d.Lw != d.Wy) return false;
   if (d.Ld != d.Di || d.Lh != d.Hi || d.Lw != d.Wi) return false;  // "same" convolution: source plane = output plane
-  if (!three_taps_f8(d.th, d.bh) || !three_taps_f8(d.tw, d.bw)) return false;
+  if (!three_taps(d.th, d.bh) || !three_taps(d.tw, d.bw)) return false;
   if (d.td.count < 1 || d.td.count > 3) return false;
   if (d.Npad % 64 || d.Lh < 6 || d.Lw < 6 || d.Lw > 64) return false;
   if (d.Lh % 16 == 0 && d.Lw % 16 == 0) return false;      // whole 16 x 16 regions: the region kernel has less halo
@@ -427,8 +422,7 @@ bool plan_flat8(const rehr_gather_gemm_desc& d, Flat8Params& p, int nfm) {
   const int64_t need = (int64_t)d.td.count * 16 * d.Npad * p.kchunks * 32 * 4;
   if (need >= (1ll << 32) - 64) return false;
   p.up_bytes = (uint32_t)need;
-  const int64_t tot = (int64_t)d.N * d.Di * d.Hi * d.Wi * 4;
-  if (tot * d.ldx1 >= (1ll << 32) - 64 || (d.x2 && tot * d.ldx2 >= (1ll << 32) - 64)) return false;
+  if (!gg_src_fits(d, (int64_t)d.N * d.Di * d.Hi * d.Wi, 4)) return false;   // one buffer over the whole batch
   if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return false;
   if (d.Npad / 64 > 65535) return false;
   const int64_t xfl = (int64_t)2 * (p.rows * p.RP + F8_LDX + 4), efl = (int64_t)nfm * 2 * 4 * 2 * 16 * 64;

@@ -20,6 +20,7 @@
 //             threads without a share of the last staging piece): fetch and staging run in the shadow
 //             of the MFMAs instead of between them, laid out per step (see kgroup).
 #include "common.h"
+#include "gg_shared.h"   // three_taps()
 #include "wgrad_shared.h"
 #include <cstdlib>
 #include <type_traits>
@@ -31,8 +32,7 @@ namespace {
 #endif
 
 constexpr int RH = 4, RW = 16;           // outputs per staged region = 2 x 8 tiles
-constexpr int XH = RH + 2, XW = RW + 2;  // input patch
-constexpr int YV = RH * RW, XV = XH * XW;
+constexpr int XH = RH + 2;               // rows of the input patch (6 x 18: two more than the outputs each way)
 
 struct WWParams {
   rehr_wgrad_desc d;
@@ -543,16 +543,10 @@ int launch_ww(const WWParams& p, dim3 grid, hipStream_t stream) {
   return REHR_OK;
 }
 
-bool three_taps_w(const rehr_axis_taps& t, int b) {
-  if (t.count != 3) return false;
-  const int o0 = b + t.off0, o1 = b + t.off0 + t.offs, o2 = b + t.off0 + 2 * t.offs;
-  return (o1 == 0) && ((o0 == -1 && o2 == 1) || (o0 == 1 && o2 == -1));
-}
-
 bool plan(const rehr_wgrad_desc& d, WWParams& p) {
   if (d.debug_flags & REHR_DBG_WGRAD_DIRECT) return false;
   if (d.sd != 1 || d.sh != 1 || d.sw != 1) return false;
-  if (!three_taps_w(d.th, d.bh) || !three_taps_w(d.tw, d.bw)) return false;
+  if (!three_taps(d.th, d.bh) || !three_taps(d.tw, d.bw)) return false;
   if (d.td.count < 1 || d.td.count > 256) return false;  // any number of depth taps (feature_fuse: 128): one grid.z each
   if (d.Hg != d.Lh || d.Wg != d.Lw) return false;
   if (d.Ca < 16 || d.Cg < 16 || d.Ca % 4 || d.Cg % 4) return false;
