@@ -233,9 +233,11 @@ typedef struct {
 int64_t rehr_wgrad_bf16_workspace_bytes(const rehr_wgrad_desc* d);
 int rehr_wgrad_bf16(const rehr_wgrad_desc* d, void* stream);
 int64_t rehr_wgrad_workspace_bytes(const rehr_wgrad_desc* d);
-/* 1 when rehr_wgrad_f32 will take the Winograd path for this descriptor (unit stride,
- * taps {-1,0,+1} over H and W, >= 64 channels on both sides): the products are formed
- * in the transform domain, 16 per 2x2 output tile and depth tap instead of 36.       */
+/* 1 when rehr_wgrad_f32 will take a transform-domain path for this descriptor: F(2x2,3x3)
+ * (unit stride, taps {-1,0,+1} over H and W, >= 16 channels on both sides: 16 products per
+ * 2x2 output tile and depth tap instead of 36) or F(2x2,2x2) (stride-2 four-tap transposed
+ * taps over H and W, >= 64 channels, no dbias: 9 instead of 16).  The same route decision
+ * sizes rehr_wgrad_workspace_bytes and drives the launch.                              */
 int rehr_wgrad_uses_winograd(const rehr_wgrad_desc* d);
 int rehr_wgrad_f32(const rehr_wgrad_desc* d, void* stream);
 

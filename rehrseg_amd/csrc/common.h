@@ -28,6 +28,19 @@ extern thread_local int rehr_last_hip_error_code;  // defined in elementwise.hip
     }                                                         \
   } while (0)
 
+// Raises the dynamic-LDS limit of KERN to `bytes` at the first call of each instantiation (per process, not per device).
+template <auto KERN>
+int set_dyn_lds_once(int bytes) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) !=
+        hipSuccess)
+      return REHR_EHIP;
+    attr_set = true;
+  }
+  return REHR_OK;
+}
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher places on
 // the same XCD (b % 8 equal) become consecutive logical ids, so neighbouring
 // tiles (shared halo / shared weight panel) hit the same 4 MiB L2.

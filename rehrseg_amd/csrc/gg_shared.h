@@ -4,6 +4,7 @@
 // (4 = fp32, 2 = bf16).  A wrong range check here is an out-of-bounds access on the device: fix it in this file only.
 #pragma once
 #include "common.h"
+#include "taps.h"   // span(), three_taps(), BUF_LIMIT
 
 // ---- plan of one launch / of the phases that share one grid (kernel arguments: the layout is part of the kernels) ----
 struct GGParams {
@@ -38,8 +39,8 @@ __device__ __forceinline__ bool interleaved_block(int b, int m_tiles, int n_tile
   return mt < m_tiles;
 }
 
-// ---- range checks: raw buffer loads take 32-bit byte offsets ----
-constexpr int64_t GG_BUF_LIMIT = (1ll << 32) - 64;
+// ---- range checks: raw buffer loads take 32-bit byte offsets (the limit itself: taps.h) ----
+constexpr int64_t GG_BUF_LIMIT = BUF_LIMIT;
 
 // bytes of the weight panel wp[tap][Npad][Cin] up to the last tap the descriptor can reach
 inline int64_t gg_wp_bytes(const rehr_gather_gemm_desc& d, int es) {
@@ -54,26 +55,6 @@ inline int64_t gg_wp_bytes(const rehr_gather_gemm_desc& d, int es) {
 inline bool gg_src_fits(const rehr_gather_gemm_desc& d, int64_t vox, int es) {
   const int64_t b = vox * es;
   return b * d.ldx1 < GG_BUF_LIMIT && (!d.x2 || b * d.ldx2 < GG_BUF_LIMIT);
-}
-
-// ---- tap geometry ----
-// smallest / largest source offset of an axis' taps relative to the lattice point
-inline void span(const rehr_axis_taps& t, int b, int* mn, int* mx) {
-  int lo = b + t.off0, hi = lo;
-  for (int j = 1; j < t.count; ++j) {
-    const int o = b + t.off0 + t.offs * j;
-    if (o < lo) lo = o;
-    if (o > hi) hi = o;
-  }
-  *mn = lo;
-  *mx = hi;
-}
-
-// the taps of a unit-stride "same" 3-tap axis: offsets -1, 0, +1 in either order (what the F(2x2,3x3) kernels transform)
-inline bool three_taps(const rehr_axis_taps& t, int b) {
-  if (t.count != 3) return false;
-  const int o0 = b + t.off0, o1 = b + t.off0 + t.offs, o2 = b + t.off0 + 2 * t.offs;
-  return (o1 == 0) && ((o0 == -1 && o2 == 1) || (o0 == 1 && o2 == -1));
 }
 
 // ---- validation: everything a kernel of the family relies on without checking it again ----

@@ -523,14 +523,8 @@ int launch_wg_bf16(const WGParams& p, hipStream_t stream) {
   constexpr int WGK = 4 / (WGA * WGG);
   constexpr size_t red = (size_t)(WGK - 1) * ((B / WGA / 32) * (B / WGG / 32) * 16) * 64 * 4;
   if (red > smem) smem = red;
-  auto kern = wgrad_bf16_kernel<B, WGA, WGG, BKV>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
+  constexpr auto kern = wgrad_bf16_kernel<B, WGA, WGG, BKV>;
+  if (set_dyn_lds_once<kern>((int)smem) != REHR_OK) return REHR_EHIP;
   dim3 grid(p.T * p.a_tiles * p.c_tiles, p.splits, 1);
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, stream, p);
   REHR_LAUNCH_CHECK();
@@ -556,13 +550,10 @@ int plan(const rehr_wgrad_desc& d, WGParams& p, int es = 4) {
   int t = tile_for(d.Ca);
   const int tg = tile_for(d.Cg);
   if (tg < t) t = tg;
-  p.a_tiles = (d.Ca + t - 1) / t;
-  p.c_tiles = (d.Cg + t - 1) / t;
-  p.Capad = p.a_tiles * t;
-  p.Cgpad = p.c_tiles * t;
+  set_slab_geometry(p, d.Ca, d.Cg, t);
   p.kv_total = (int64_t)d.N * d.Ld * d.Lh * d.Lw;
   const int64_t gbytes = (int64_t)d.N * d.Dg * d.Hg * d.Wg * d.ldg * es;
-  if (p.kv_total >= (1ll << 31) - 4096 || gbytes >= (1ll << 32) - 64) return REHR_ENOSUP;
+  if (p.kv_total >= (1ll << 31) - 4096 || !fits_buffer(gbytes)) return REHR_ENOSUP;
   p.g_bytes = (uint32_t)gbytes;
   const int bkv = es == 2 ? 64 : bkv_for(t);
   const int64_t tiles = (int64_t)p.T * p.a_tiles * p.c_tiles;
@@ -572,24 +563,10 @@ int plan(const rehr_wgrad_desc& d, WGParams& p, int es = 4) {
   if (want > max_by_k) want = max_by_k;
   if (want < 1) want = 1;
   if (want > 1024) want = 1024;
-  {
-    // All blocks take the same time and 512 are resident at once (256 CUs x 2): pick the
-    // split count near `want` whose last round of blocks is fullest (tail effect).
-    int64_t best = want;
-    double best_eff = 0.0;
-    const int64_t lo = want > 2 ? want - want / 3 : 1;
-    int64_t hi = want + want / 2 + 1;
-    if (hi > max_by_k) hi = max_by_k > want ? max_by_k : want;
-    for (int64_t s = lo; s <= hi; ++s) {
-      const double rounds = (double)(tiles * s) / 512.0;
-      const double eff = rounds / (double)(int64_t)(rounds + 0.999999);
-      if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
-    }
-    want = best;
-  }
+  want = splits_fullest_last_round(want, max_by_k, tiles);
   int64_t per = (p.kv_total + want - 1) / want;
   per = (per + bkv - 1) / bkv * bkv;
-  if ((int64_t)per * d.ldl * es >= (1ll << 32) - 64) return REHR_ENOSUP;
+  if (!fits_buffer((int64_t)per * d.ldl * es)) return REHR_ENOSUP;
   p.kv_per_split = per;
   p.splits = (int)((p.kv_total + per - 1) / per);
   p.mg_vox = make_magic((uint32_t)(d.Ld * d.Lh * d.Lw));
@@ -598,26 +575,14 @@ int plan(const rehr_wgrad_desc& d, WGParams& p, int es = 4) {
   return REHR_OK;
 }
 
-int64_t ws_bytes(const WGParams& p) {
-  int64_t f = (int64_t)p.splits * p.T * p.Capad * p.Cgpad;
-  f += (int64_t)p.splits * p.d.Ca;  // bias slab
-  return f * (int64_t)sizeof(float);
-}
-
 template <int B, int WGA, int WGG, int BKV>
 int launch_wg(const WGParams& p, hipStream_t stream) {
   size_t smem = (size_t)2 * BKV * ((B + 4) + (B + 4)) * sizeof(float);
   constexpr int WGK = 4 / (WGA * WGG);
   constexpr size_t red = (size_t)(WGK - 1) * ((B / WGA / 32) * (B / WGG / 32) * 16 + (B / WGA / 32)) * 64 * 4;
   if (red > smem) smem = red;
-  auto kern = wgrad_kernel<B, B, WGA, WGG, BKV>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
+  constexpr auto kern = wgrad_kernel<B, B, WGA, WGG, BKV>;
+  if (set_dyn_lds_once<kern>((int)smem) != REHR_OK) return REHR_EHIP;
   dim3 grid(p.T * p.a_tiles * p.c_tiles, p.splits, 1);
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, stream, p);
   REHR_LAUNCH_CHECK();
@@ -629,38 +594,77 @@ int plan_bf16(const rehr_wgrad_desc& d, WGParams& p) {
   return plan(d, p, 2);
 }
 
+// ---- the route: which kernel takes a descriptor, with what plan and how much workspace.  Decided in ONE place per
+// precision; the size queries, rehr_wgrad_uses_winograd and the launches all read the same WGRoute. ----
+enum Route { ROUTE_WINO, ROUTE_WINO22, ROUTE_BRICK, ROUTE_SLAB };
+template <class BRICK>   // BrickPlanOut (fp32) or BrickBf16
+struct WGRoute {
+  Route route;
+  WGParams p;         // brick / slab routes: tiles, splits and slab geometry (the brick planners override plan()'s)
+  BRICK brick;        // brick route only
+  int64_t ws_bytes;   // workspace the route needs
+};
+
+int64_t slab_bytes(const WGParams& p) { return (int64_t)p.splits * p.T * p.Capad * p.Cgpad * (int64_t)sizeof(float); }
+
+// a size query may come before the destination is allocated: the planners only ask whether dst is null
+rehr_wgrad_desc with_dst(const rehr_wgrad_desc& d) {
+  rehr_wgrad_desc q = d;
+  if (!q.dst) q.dst = reinterpret_cast<float*>(16);
+  return q;
+}
+
+// fp32: Winograd F(2x2,3x3) (2.25x fewer multiplications) -> F(2x2,2x2) (stride-2 4-tap transposed convs: 1.78x fewer)
+// -> LDS bricks -> per-tap slabs
+int route_f32(const rehr_wgrad_desc& d, WGRoute<BrickPlanOut>& r) {
+  const int rc = plan(d, r.p);
+  if (rc != REHR_OK) return rc;
+  if ((r.ws_bytes = wino_wgrad_workspace_bytes(d)) > 0) { r.route = ROUTE_WINO; return REHR_OK; }
+  if ((r.ws_bytes = wino22_wgrad_workspace_bytes(d)) > 0) { r.route = ROUTE_WINO22; return REHR_OK; }
+  r.route = wgrad_brick_plan(d, r.p, r.brick) ? ROUTE_BRICK : ROUTE_SLAB;
+  r.ws_bytes = slab_bytes(r.p) + (int64_t)r.p.splits * d.Ca * (int64_t)sizeof(float);  // + bias slab, wanted or not
+  return REHR_OK;
+}
+
+// bf16: unit-stride 3x3(x3) taps take both operands as LDS bricks (REHR_DBG_WGRAD_DIRECT keeps the per-tap slab kernel)
+int route_bf16(const rehr_wgrad_desc& d, WGRoute<BrickBf16>& r) {
+  const int rc = plan_bf16(d, r.p);
+  if (rc != REHR_OK) return rc;
+  const bool brick = !(d.debug_flags & REHR_DBG_WGRAD_DIRECT) && wgrad_brick_bf16_plan(d, r.p, r.brick);
+  r.route = brick ? ROUTE_BRICK : ROUTE_SLAB;
+  r.ws_bytes = slab_bytes(r.p);
+  return REHR_OK;
+}
+
+// what the brick / slab launches check before anything runs
+template <class BRICK>
+int check_launch(const WGRoute<BRICK>& r) {
+  const rehr_wgrad_desc& d = r.p.d;
+  if (!d.workspace || d.workspace_bytes < r.ws_bytes) return REHR_EINVAL;
+  if (r.p.splits > 65535) return REHR_EINVAL;   // grid.y
+  return REHR_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t rehr_wgrad_bf16_workspace_bytes(const rehr_wgrad_desc* dp) {
   if (!dp) return REHR_EINVAL;
-  WGParams p;
-  rehr_wgrad_desc d = *dp;
-  if (!d.dst) d.dst = reinterpret_cast<float*>(16);
-  const int rc = plan_bf16(d, p);
-  if (rc != REHR_OK) return rc;
-  BrickBf16 bo;
-  WGParams pb = p;
-  if (!(d.debug_flags & REHR_DBG_WGRAD_DIRECT) && wgrad_brick_bf16_plan(d, pb, bo))
-    return (int64_t)pb.splits * pb.T * pb.Capad * pb.Cgpad * (int64_t)sizeof(float);
-  return (int64_t)p.splits * p.T * p.Capad * p.Cgpad * (int64_t)sizeof(float);
+  WGRoute<BrickBf16> r;
+  const int rc = route_bf16(with_dst(*dp), r);
+  return rc != REHR_OK ? rc : r.ws_bytes;
 }
 
 extern "C" int rehr_wgrad_bf16(const rehr_wgrad_desc* dp, void* stream) {
   if (!dp) return REHR_EINVAL;
-  WGParams p;
-  int rc = plan_bf16(*dp, p);
+  WGRoute<BrickBf16> r;
+  int rc = route_bf16(*dp, r);
+  if (rc == REHR_OK) rc = check_launch(r);
   if (rc != REHR_OK) return rc;
-  BrickBf16 bo;
-  // unit-stride 3x3(x3) taps: both operands as LDS bricks (REHR_DBG_WGRAD_DIRECT keeps the per-tap slab kernel)
-  const bool brick = !(dp->debug_flags & REHR_DBG_WGRAD_DIRECT) && wgrad_brick_bf16_plan(*dp, p, bo);
-  const rehr_wgrad_desc& d = p.d;
-  if (!d.workspace || d.workspace_bytes < (int64_t)p.splits * p.T * p.Capad * p.Cgpad * (int64_t)sizeof(float))
-    return REHR_EINVAL;
-  if (p.splits > 65535) return REHR_EINVAL;
+  WGParams& p = r.p;
   p.slab_bias = nullptr;
   hipStream_t st = (hipStream_t)stream;
-  if (brick) {
-    rc = wgrad_brick_bf16_launch(p, bo, st);
+  if (r.route == ROUTE_BRICK) {
+    rc = wgrad_brick_bf16_launch(p, r.brick, st);
   } else {
     const int t = p.Capad / p.a_tiles;
     if (t == 128) rc = launch_wg_bf16<128, 2, 2, 64>(p, st);
@@ -675,48 +679,34 @@ extern "C" int rehr_wgrad_bf16(const rehr_wgrad_desc* dp, void* stream) {
 
 extern "C" int64_t rehr_wgrad_workspace_bytes(const rehr_wgrad_desc* dp) {
   if (!dp) return REHR_EINVAL;
-  WGParams p;
-  rehr_wgrad_desc d = *dp;
-  if (!d.dst) d.dst = reinterpret_cast<float*>(16);  // size query may come before allocation
-  const int rc = plan(d, p);
-  if (rc != REHR_OK) return rc;
-  const int64_t wino = wino_wgrad_workspace_bytes(d);
-  if (wino > 0) return wino;
-  const int64_t wino22 = wino22_wgrad_workspace_bytes(d);
-  if (wino22 > 0) return wino22;
-  BrickPlanOut bo;
-  WGParams pb = p;
-  if (wgrad_brick_plan(d, pb, bo)) return ws_bytes(pb);
-  return ws_bytes(p);
+  WGRoute<BrickPlanOut> r;
+  const int rc = route_f32(with_dst(*dp), r);
+  return rc != REHR_OK ? rc : r.ws_bytes;
 }
 
 extern "C" int rehr_wgrad_uses_winograd(const rehr_wgrad_desc* dp) {
   if (!dp) return 0;
-  WGParams p;
-  rehr_wgrad_desc d = *dp;
-  if (!d.dst) d.dst = reinterpret_cast<float*>(16);
-  if (plan(d, p) != REHR_OK) return 0;
-  return (wino_wgrad_workspace_bytes(d) > 0 || wino22_wgrad_workspace_bytes(d) > 0) ? 1 : 0;
+  WGRoute<BrickPlanOut> r;
+  if (route_f32(with_dst(*dp), r) != REHR_OK) return 0;
+  return (r.route == ROUTE_WINO || r.route == ROUTE_WINO22) ? 1 : 0;
 }
 
 extern "C" int rehr_wgrad_f32(const rehr_wgrad_desc* dp, void* stream) {
   if (!dp) return REHR_EINVAL;
-  WGParams p;
-  int rc = plan(*dp, p);
+  WGRoute<BrickPlanOut> r;
+  int rc = route_f32(*dp, r);
   if (rc != REHR_OK) return rc;
-  rc = wino_wgrad_try(*dp, (hipStream_t)stream);  // 2.25x fewer multiplications where it applies
-  if (rc != REHR_ENOSUP) return rc;
-  rc = wino22_wgrad_try(*dp, (hipStream_t)stream);  // stride-2 4-tap transposed convs: 1.78x fewer
-  if (rc != REHR_ENOSUP) return rc;
-  BrickPlanOut bo;
-  const bool brick = wgrad_brick_plan(*dp, p, bo);  // overrides tiles / splits / slab geometry when it applies
-  const rehr_wgrad_desc& d = p.d;
-  if (!d.workspace || d.workspace_bytes < ws_bytes(p)) return REHR_EINVAL;
-  if (p.splits > 65535) return REHR_EINVAL;
-  p.slab_bias = d.dbias ? d.workspace + (int64_t)p.splits * p.T * p.Capad * p.Cgpad : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  if (brick) {
-    rc = wgrad_brick_launch(p, bo, st);
+  // the transform-domain files plan, check the workspace against the size they reported and launch on their own
+  if (r.route == ROUTE_WINO) return wino_wgrad_try(*dp, st);
+  if (r.route == ROUTE_WINO22) return wino22_wgrad_try(*dp, st);
+  rc = check_launch(r);
+  if (rc != REHR_OK) return rc;
+  WGParams& p = r.p;
+  const rehr_wgrad_desc& d = p.d;
+  p.slab_bias = d.dbias ? d.workspace + (int64_t)p.splits * p.T * p.Capad * p.Cgpad : nullptr;
+  if (r.route == ROUTE_BRICK) {
+    rc = wgrad_brick_launch(p, r.brick, st);
   } else {
     const int t = p.Capad / p.a_tiles;
     if (t == 128) rc = launch_wg<128, 2, 2, 32>(p, st);

@@ -21,11 +21,7 @@ constexpr int MAXX = 13;                                     // halo rows staged
 
 struct BrickParams {
   WGParams w;
-  int HD, HH, HW;        // halo extents
-  int mind, minh, minw;  // smallest tap offset per axis (incl. the lattice->source offset b)
-  int nb_d, nb_h, nb_w;  // bricks per sample along each axis
-  int64_t nbricks;
-  int bricks_per_split;
+  BrickPlanOut o;
 };
 
 // TPW = taps per wave is a compile-time constant so the k-step body is branch-free: a wave
@@ -36,7 +32,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Ys = smem;                 // [BVOX][LDY]
   float* Xs = smem + BVOX * LDY;    // [hvox][LDX]
-  const int hvox = p.HD * p.HH * p.HW;
+  const int hvox = p.o.HD * p.o.HH * p.o.HW;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -57,10 +53,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
     const int jw = tt % d.tw.count;
     const int jh = (tt / d.tw.count) % d.th.count;
     const int jd = tt / (d.tw.count * d.th.count);
-    const int od_ = d.bd + d.td.off0 + d.td.offs * jd - p.mind;
-    const int oh_ = d.bh + d.th.off0 + d.th.offs * jh - p.minh;
-    const int ow_ = d.bw + d.tw.off0 + d.tw.offs * jw - p.minw;
-    tapbase[j] = (od_ * p.HH + oh_) * p.HW + ow_;
+    const int od_ = d.bd + d.td.off0 + d.td.offs * jd - p.o.mind;
+    const int oh_ = d.bh + d.th.off0 + d.th.offs * jh - p.o.minh;
+    const int ow_ = d.bw + d.tw.off0 + d.tw.offs * jw - p.o.minw;
+    tapbase[j] = (od_ * p.o.HH + oh_) * p.o.HW + ow_;
   }
 
   f32x16 acc[TPW];
@@ -76,9 +72,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
   const int col = lane & 31, half = lane >> 5;
   const int q = tid & 7, r0 = tid >> 3;  // staging: 8 x 16-byte pieces per 32-channel row
 
-  const int64_t br_begin = (int64_t)split * p.bricks_per_split;
-  int64_t br_end = br_begin + p.bricks_per_split;
-  if (br_end > p.nbricks) br_end = p.nbricks;
+  const int64_t br_begin = (int64_t)split * p.o.bricks_per_split;
+  int64_t br_end = br_begin + p.o.bricks_per_split;
+  if (br_end > p.o.nbricks) br_end = p.o.nbricks;
 
   // Halo pieces owned by this thread: the (hd,hh,hw) split of a halo row does not depend on
   // the brick, so it is done once here (no divisions inside the brick loop).
@@ -86,9 +82,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
 #pragma unroll
   for (int i = 0; i < MAXX; ++i) {
     const int hv = r0 + 32 * i;
-    const int hw_ = hv % p.HW;
-    const int t2 = hv / p.HW;
-    hcoord[i] = hv < hvox ? (((t2 / p.HH) << 20) | ((t2 % p.HH) << 10) | hw_) : -1;
+    const int hw_ = hv % p.o.HW;
+    const int t2 = hv / p.o.HW;
+    hcoord[i] = hv < hvox ? (((t2 / p.o.HH) << 20) | ((t2 % p.o.HH) << 10) | hw_) : -1;
   }
   const __amdgpu_buffer_rsrc_t rl_ = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(d.l), 0, (uint32_t)((int64_t)d.N * lvox * d.ldl * 4), 0x00020000);
@@ -105,11 +101,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
   auto fetch = [&](int64_t br) {
     const bool live = br < br_end;
     const int64_t bb = live ? br : br_begin;
-    const int bw_ = (int)(bb % p.nb_w);
-    int64_t r = bb / p.nb_w;
-    const int bh_ = (int)(r % p.nb_h); r /= p.nb_h;
-    const int bd_ = (int)(r % p.nb_d);
-    const int n = (int)(r / p.nb_d);
+    const int bw_ = (int)(bb % p.o.nb_w);
+    int64_t r = bb / p.o.nb_w;
+    const int bh_ = (int)(r % p.o.nb_h); r /= p.o.nb_h;
+    const int bd_ = (int)(r % p.o.nb_d);
+    const int n = (int)(r / p.o.nb_d);
     const int od0 = bd_ * BD, oh0 = bh_ * BH, ow0 = bw_ * BW;
     const uint32_t lbase = (uint32_t)n * (uint32_t)lvox;
 #pragma unroll
@@ -121,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
                            (uint32_t)(a0 + q * 4) * 4u;
       ry[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl_, ok ? off : l_oob, 0, 0));
     }
-    const int gd0 = od0 + p.mind, gh0 = oh0 + p.minh, gw0 = ow0 + p.minw;
+    const int gd0 = od0 + p.o.mind, gh0 = oh0 + p.o.minh, gw0 = ow0 + p.o.minw;
     const uint32_t gbase = (uint32_t)n * (uint32_t)gvox;
 #pragma unroll
     for (int i = 0; i < MAXX; ++i) {
@@ -157,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
     float a0_, x0_[TPW], a1_, x1_[TPW];
     auto lds_read = [&](int ks, float& a, float (&x)[TPW]) {
       const int v = 2 * ks;
-      const int row0 = ((v >> 6) * p.HH + ((v >> 3) & 7)) * p.HW + (v & 7);
+      const int row0 = ((v >> 6) * p.o.HH + ((v >> 3) & 7)) * p.o.HW + (v & 7);
       a = yb[v * LDY];
 #pragma unroll
       for (int j = 0; j < TPW; ++j) x[j] = xb[(row0 + tapbase[j]) * LDX];
@@ -200,16 +196,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_brick_kernel(const BrickParams p
   }
 }
 
-void axis_span(const rehr_axis_taps& t, int b, int* mn, int* mx) {
-  int lo = b + t.off0, hi = b + t.off0;
-  for (int j = 1; j < t.count; ++j) {
-    const int o = b + t.off0 + t.offs * j;
-    if (o < lo) lo = o;
-    if (o > hi) hi = o;
-  }
-  *mn = lo;
-  *mx = hi;
-}
+// dynamic LDS of a block: the lattice brick and `hvox` halo voxels
+size_t lds_bytes(int64_t hvox) { return (size_t)(BVOX * LDY + hvox * LDX) * sizeof(float); }
 
 }  // namespace
 
@@ -228,23 +216,19 @@ bool wgrad_brick_plan(const rehr_wgrad_desc& d, WGParams& w, BrickPlanOut& out) 
   const int64_t padded = nb_d * BD * nb_h * BH * nb_w * BW;
   if (padded * 10 > (int64_t)d.Ld * d.Lh * d.Lw * 13) return false;
   int mn[3], mx[3];
-  axis_span(d.td, d.bd, &mn[0], &mx[0]);
-  axis_span(d.th, d.bh, &mn[1], &mx[1]);
-  axis_span(d.tw, d.bw, &mn[2], &mx[2]);
+  span(d.td, d.bd, &mn[0], &mx[0]);
+  span(d.th, d.bh, &mn[1], &mx[1]);
+  span(d.tw, d.bw, &mn[2], &mx[2]);
   const int HD = BD + mx[0] - mn[0], HH = BH + mx[1] - mn[1], HW = BW + mx[2] - mn[2];
   const int64_t hvox = (int64_t)HD * HH * HW;
-  const size_t smem = (size_t)(BVOX * LDY + hvox * LDX) * sizeof(float);
-  if (smem > 80 * 1024 || hvox > MAXX * 32 || HH > 1023 || HW > 1023) return false;
+  if (lds_bytes(hvox) > 80 * 1024 || hvox > MAXX * 32 || HH > 1023 || HW > 1023) return false;
   // buffer-addressed operands: 32-bit byte offsets over the whole tensors
-  if ((int64_t)d.N * d.Ld * d.Lh * d.Lw * d.ldl * 4 >= (1ll << 32) - 64 ||
-      (int64_t)d.N * d.Dg * d.Hg * d.Wg * d.ldg * 4 >= (1ll << 32) - 64)
+  if (!fits_buffer((int64_t)d.N * d.Ld * d.Lh * d.Lw * d.ldl * 4) ||
+      !fits_buffer((int64_t)d.N * d.Dg * d.Hg * d.Wg * d.ldg * 4))
     return false;
   w.d = d;
   w.T = T;
-  w.a_tiles = (d.Ca + 31) / 32;
-  w.c_tiles = (d.Cg + 31) / 32;
-  w.Capad = w.a_tiles * 32;
-  w.Cgpad = w.c_tiles * 32;
+  set_slab_geometry(w, d.Ca, d.Cg, 32);
   w.kv_total = (int64_t)d.N * d.Ld * d.Lh * d.Lw;
   out.HD = HD; out.HH = HH; out.HW = HW;
   out.mind = mn[0]; out.minh = mn[1]; out.minw = mn[2];
@@ -256,48 +240,24 @@ bool wgrad_brick_plan(const rehr_wgrad_desc& d, WGParams& w, BrickPlanOut& out) 
   const int64_t max_by_k = (out.nbricks + 3) / 4;
   if (want > max_by_k) want = max_by_k;
   if (want < 1) want = 1;
-  {
-    int64_t best = want;
-    double best_eff = 0.0;
-    const int64_t lo = want > 2 ? want - want / 3 : 1;
-    int64_t hi = want + want / 2 + 1;
-    if (hi > max_by_k) hi = max_by_k > want ? max_by_k : want;
-    for (int64_t s = lo; s <= hi; ++s) {
-      const double rounds = (double)(tiles * s) / 512.0;
-      const double eff = rounds / (double)(int64_t)(rounds + 0.999999);
-      if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
-    }
-    want = best;
-  }
+  want = splits_fullest_last_round(want, max_by_k, tiles);
   if (want > 65535) want = 65535;
   out.bricks_per_split = (int)((out.nbricks + want - 1) / want);
   w.splits = (int)((out.nbricks + out.bricks_per_split - 1) / out.bricks_per_split);
   w.kv_per_split = 0;
-  out.smem = smem;
   return true;
 }
 
 int wgrad_brick_launch(const WGParams& w, const BrickPlanOut& o, hipStream_t stream) {
-  BrickParams p;
-  p.w = w;
-  p.HD = o.HD; p.HH = o.HH; p.HW = o.HW;
-  p.mind = o.mind; p.minh = o.minh; p.minw = o.minw;
-  p.nb_d = o.nb_d; p.nb_h = o.nb_h; p.nb_w = o.nb_w;
-  p.nbricks = o.nbricks;
-  p.bricks_per_split = o.bricks_per_split;
+  const BrickParams p{w, o};
+  const size_t smem = lds_bytes((int64_t)o.HD * o.HH * o.HW);
   dim3 grid(w.a_tiles * w.c_tiles, w.splits, 1);
   const int tpw = (w.T + 3) / 4;
 #define BRICK_CASE(N_)                                                                                   \
-  case N_: {                                                                                             \
-    static bool attr_set = false;                                                                        \
-    if (!attr_set) {                                                                                     \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_brick_kernel<N_>),                     \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)      \
-        return REHR_EHIP;                                                                                \
-      attr_set = true;                                                                                   \
-    }                                                                                                    \
-    hipLaunchKernelGGL(wgrad_brick_kernel<N_>, grid, dim3(256), o.smem, stream, p);                      \
-  } break;
+  case N_:                                                                                               \
+    if (set_dyn_lds_once<wgrad_brick_kernel<N_>>(80 * 1024) != REHR_OK) return REHR_EHIP;                \
+    hipLaunchKernelGGL(wgrad_brick_kernel<N_>, grid, dim3(256), smem, stream, p);                        \
+    break;
   switch (tpw) {
     BRICK_CASE(1) BRICK_CASE(2) BRICK_CASE(3) BRICK_CASE(4) BRICK_CASE(5) BRICK_CASE(6) BRICK_CASE(7)
     default: return REHR_ENOSUP;

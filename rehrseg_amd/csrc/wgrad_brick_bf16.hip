@@ -221,23 +221,18 @@ bool wgrad_brick_bf16_plan(const rehr_wgrad_desc& d, WGParams& w, BrickBf16& o) 
   const int KD = d.td.count;
   if ((KD != 3 && KD != 1) || d.th.count != 3 || d.tw.count != 3) return false;
   // taps must be the contiguous {-1, 0, +1} window (any order) on the axes that have three
-  auto win = [](const rehr_axis_taps& t, int b, int* mn) {
-    int lo = b + t.off0, hi = lo;
-    for (int j = 1; j < t.count; ++j) {
-      const int v = b + t.off0 + t.offs * j;
-      lo = v < lo ? v : lo;
-      hi = v > hi ? v : hi;
-    }
-    *mn = lo;
-    return hi - lo == t.count - 1 && (t.offs == 1 || t.offs == -1 || t.count == 1);
+  auto window = [](const rehr_axis_taps& t, int b, int* mn) {
+    int mx;
+    span(t, b, mn, &mx);
+    return mx - *mn == t.count - 1 && (t.offs == 1 || t.offs == -1 || t.count == 1);
   };
-  if (!win(d.td, d.bd, &o.mind) || !win(d.th, d.bh, &o.minh) || !win(d.tw, d.bw, &o.minw)) return false;
+  if (!window(d.td, d.bd, &o.mind) || !window(d.th, d.bh, &o.minh) || !window(d.tw, d.bw, &o.minw)) return false;
   if (d.Ca % 8 || d.Cg % 8 || d.ldl % 8 || d.ldg % 8) return false;
   if (d.Ld < 2 || d.Lh < 8 || d.Lw < 16) return false;
   const int64_t nb_d = (d.Ld + BD - 1) / BD, nb_h = (d.Lh + BH - 1) / BH, nb_w = (d.Lw + BW - 1) / BW;
   if (nb_d * BD * nb_h * BH * nb_w * BW * 10 > (int64_t)d.Ld * d.Lh * d.Lw * 13) return false;
   const int64_t gimg = (int64_t)d.Dg * d.Hg * d.Wg * d.ldg * 2, limg = (int64_t)d.Ld * d.Lh * d.Lw * d.ldl * 2;
-  if (gimg >= (1ll << 32) - 64 || limg >= (1ll << 32) - 64) return false;
+  if (!fits_buffer(gimg) || !fits_buffer(limg)) return false;
   o.nb_d = (int)nb_d; o.nb_h = (int)nb_h; o.nb_w = (int)nb_w;
   o.tiles_per_img = (int)(nb_d * nb_h * nb_w);
   const int64_t ntiles = (int64_t)d.N * o.tiles_per_img;
@@ -245,10 +240,7 @@ bool wgrad_brick_bf16_plan(const rehr_wgrad_desc& d, WGParams& w, BrickBf16& o) 
   o.ntiles = (int)ntiles;
   w.d = d;
   w.T = KD * 9;
-  w.a_tiles = (d.Ca + 31) / 32;
-  w.c_tiles = (d.Cg + 31) / 32;
-  w.Capad = w.a_tiles * 32;
-  w.Cgpad = w.c_tiles * 32;
+  set_slab_geometry(w, d.Ca, d.Cg, 32);
   const int pairs = w.a_tiles * w.c_tiles;
   int64_t want = 256 / pairs;            // one block per CU
   if (want < 1) want = 1;
@@ -265,14 +257,8 @@ static int wgrad_brick_bf16_launch_t(const WGParams& w, const BrickBf16& o, hipS
   const int hvox = (BD + KD - 1) * (BH + 2) * (BW + 2);
   const size_t smem = (size_t)((hvox + RPP - 1) / RPP) * RPP * ROW + (size_t)BVOX * ROW;
   const dim3 grid(w.splits, w.a_tiles * w.c_tiles, 1);
-  auto kern = wgrad_brick_bf16_kernel<KD, NWV>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) !=
-        hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
+  constexpr auto kern = wgrad_brick_bf16_kernel<KD, NWV>;
+  if (set_dyn_lds_once<kern>(112 * 1024) != REHR_OK) return REHR_EHIP;
   hipLaunchKernelGGL(kern, grid, dim3(64 * NWV), smem, stream, w, o);
   REHR_LAUNCH_CHECK();
   return REHR_OK;

@@ -279,8 +279,7 @@ bool plan(const rehr_wgrad_desc& d, WW22Params& p) {
   p.Cgpad = p.c_tiles * 64;
   if ((int64_t)p.a_tiles * p.c_tiles > 65535) return false;
   if ((int64_t)p.Capad * p.Cgpad * 10 > (int64_t)d.Ca * d.Cg * 14) return false;
-  if ((int64_t)d.Ld * d.Lh * d.Lw * d.ldl * 4 >= (1ll << 32) - 64 ||
-      (int64_t)d.Dg * d.Hg * d.Wg * d.ldg * 4 >= (1ll << 32) - 64)
+  if (!fits_buffer((int64_t)d.Ld * d.Lh * d.Lw * d.ldl * 4) || !fits_buffer((int64_t)d.Dg * d.Hg * d.Wg * d.ldg * 4))
     return false;
   p.nphase = ah.nph * aw.nph;
   for (int i = 0; i < ah.nph; ++i)
@@ -293,27 +292,16 @@ bool plan(const rehr_wgrad_desc& d, WW22Params& p) {
     }
   // split count: whole rounds of 256 single-block CUs, >= 16 stages per block
   const int tiles = p.a_tiles * p.c_tiles * p.nphase * d.td.count;
-  int best_s = 1;
-  double best_eff = 0.0;
-  for (int k = 1; k <= 4; ++k) {
-    int s = (256 * k) / tiles;
-    if (s < 1) s = 1;
-    if ((int64_t)s * 16 > items) s = (int)(items / 16);
-    if (s < 1) s = 1;
-    const int64_t blocks = (int64_t)s * tiles;
-    const int64_t rounds = (blocks + 255) / 256;
-    const double eff = (double)blocks / (double)(rounds * 256);
-    if (eff > best_eff + 0.03) { best_eff = eff; best_s = s; }
-  }
-  p.splits = best_s;
+  p.splits = splits_whole_rounds(tiles, 256, items);
   p.items_per_split = (p.items + p.splits - 1) / p.splits;
   p.splits = (p.items + p.items_per_split - 1) / p.items_per_split;
   if (p.splits > 65535) return false;
   return true;
 }
 
-int64_t slab_floats(const WW22Params& p) {
-  return (int64_t)p.splits * p.nphase * p.d.td.count * 9 * p.Capad * p.Cgpad;
+// workspace bytes: slabs[splits][nphase*KD][9][Capad][Cgpad] and alignment slack
+int64_t need_bytes(const WW22Params& p) {
+  return (int64_t)p.splits * p.nphase * p.d.td.count * 9 * p.Capad * p.Cgpad * 4 + 64;
 }
 
 }  // namespace
@@ -321,23 +309,16 @@ int64_t slab_floats(const WW22Params& p) {
 int64_t wino22_wgrad_workspace_bytes(const rehr_wgrad_desc& d) {
   WW22Params p;
   if (!plan(d, p)) return 0;
-  return slab_floats(p) * 4 + 64;
+  return need_bytes(p);
 }
 
 int wino22_wgrad_try(const rehr_wgrad_desc& d, hipStream_t stream) {
   WW22Params p;
   if (!plan(d, p)) return REHR_ENOSUP;
-  const int64_t need = slab_floats(p) * 4 + 64;
-  if (!d.workspace || d.workspace_bytes < need || ((uintptr_t)d.workspace & 15)) return REHR_EINVAL;
+  if (!d.workspace || d.workspace_bytes < need_bytes(p) || ((uintptr_t)d.workspace & 15)) return REHR_EINVAL;
   p.slabs = d.workspace;
   const size_t smem = (size_t)2 * STG * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wino22_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-        hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
+  if (set_dyn_lds_once<wino22_wgrad_kernel>((int)smem) != REHR_OK) return REHR_EHIP;
   dim3 grid(p.splits, p.a_tiles * p.c_tiles, p.nphase * d.td.count);
   hipLaunchKernelGGL(wino22_wgrad_kernel, grid, dim3(NTH), smem, stream, p);
   const int64_t total = (int64_t)p.nphase * d.td.count * d.Ca * d.Cg;

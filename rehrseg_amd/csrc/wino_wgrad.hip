@@ -20,7 +20,6 @@
 //             threads without a share of the last staging piece): fetch and staging run in the shadow
 //             of the MFMAs instead of between them, laid out per step (see kgroup).
 #include "common.h"
-#include "gg_shared.h"   // three_taps()
 #include "wgrad_shared.h"
 #include <cstdlib>
 #include <type_traits>
@@ -532,13 +531,7 @@ __global__ __launch_bounds__(256) void wino_wgrad_reduce_kernel(const WWParams p
 template <int FA, int FB, bool VIRT, int MINB_ = WWCfg<FA, FB>::MINB, int WS = 1>
 int launch_ww(const WWParams& p, dim3 grid, hipStream_t stream) {
   const size_t smem = ((size_t)2 * WWCfg<FA, FB, WS>::BUF + 128) * sizeof(float);  // + the spare pad of stage()
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wino_wgrad_kernel<FA, FB, VIRT, MINB_, WS>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
+  if (set_dyn_lds_once<wino_wgrad_kernel<FA, FB, VIRT, MINB_, WS>>((int)smem) != REHR_OK) return REHR_EHIP;
   hipLaunchKernelGGL((wino_wgrad_kernel<FA, FB, VIRT, MINB_, WS>), grid, dim3(256 * WS), smem, stream, p);
   return REHR_OK;
 }
@@ -570,8 +563,8 @@ bool plan(const rehr_wgrad_desc& d, WWParams& p) {
     const int64_t groups = ((int64_t)p.nslices + p.G - 1) / p.G;
     p.nb_w = (p.G * p.Lw2 + RW - 1) / RW;
     if ((int64_t)groups * p.nb_h * RH * p.nb_w * RW * 100 > (int64_t)p.nslices * d.Lh * d.Lw * 140) return false;
-    if ((int64_t)d.N * d.Ld * d.Lh * d.Lw * d.ldl * 4 >= (1ll << 32) - 64 ||
-        (int64_t)d.N * d.Dg * d.Hg * d.Wg * d.ldg * 4 >= (1ll << 32) - 64)
+    if (!fits_buffer((int64_t)d.N * d.Ld * d.Lh * d.Lw * d.ldl * 4) ||
+        !fits_buffer((int64_t)d.N * d.Dg * d.Hg * d.Wg * d.ldg * 4))
       return false;
     items = groups * p.nb_h * p.nb_w;
     if (items < 128) return false;  // too few stages to split over the chip: the slab kernel's finer split-K wins
@@ -604,24 +597,12 @@ bool plan(const rehr_wgrad_desc& d, WWParams& p) {
   // 32-wide group still beats the direct kernels by a wide margin (SR head: 8.2 ms -> see DESIGN)
   const int64_t limit = (p.fa * p.fb == 1) ? 21 : 14;
   if ((int64_t)p.Capad * p.Cgpad * 10 > (int64_t)d.Ca * d.Cg * limit) return false;
-  if ((int64_t)d.Ld * d.Lh * d.Lw * d.ldl * 4 >= (1ll << 32) - 64 ||
-      (int64_t)d.Dg * d.Hg * d.Wg * d.ldg * 4 >= (1ll << 32) - 64)
+  if (!fits_buffer((int64_t)d.Ld * d.Lh * d.Lw * d.ldl * 4) || !fits_buffer((int64_t)d.Dg * d.Hg * d.Wg * d.ldg * 4))
     return false;
   // split count: fill whole rounds of 256 single-block CUs, >= 16 stages per block
   const int tiles = p.a_tiles * p.c_tiles * d.td.count;
   const int slots = 256 * ((p.fa * p.fb == 1) ? 2 : 1);  // resident blocks
-  int best_s = 1;
-  double best_eff = 0.0;
-  for (int k = 1; k <= 4; ++k) {
-    int s = (slots * k) / tiles;
-    if (s < 1) s = 1;
-    if ((int64_t)s * 16 > items) s = (int)(items / 16);
-    if (s < 1) s = 1;
-    const int64_t blocks = (int64_t)s * tiles;
-    const int64_t rounds = (blocks + slots - 1) / slots;
-    const double eff = (double)blocks / (double)(rounds * slots);
-    if (eff > best_eff + 0.03) { best_eff = eff; best_s = s; }
-  }
+  int best_s = splits_whole_rounds(tiles, slots, items);
   // many splits (few channel tiles, e.g. 32 x 32 channels: 170): a multiple of 8, so that the tap-colocated grid (the
   // taps of a split on one XCD, see the kernel) gives every XCD the same number of blocks
   if (best_s >= 64 && d.td.count > 1) best_s &= ~7;
@@ -634,6 +615,8 @@ bool plan(const rehr_wgrad_desc& d, WWParams& p) {
 int64_t slab_floats(const WWParams& p) {
   return (int64_t)p.splits * p.d.td.count * 16 * p.Capad * p.Cgpad;
 }
+// workspace bytes: the slabs, the bias slab (also when dbias is null) and alignment slack
+int64_t need_bytes(const WWParams& p) { return (slab_floats(p) + (int64_t)p.splits * p.Capad) * 4 + 64; }
 
 }  // namespace
 
@@ -641,15 +624,14 @@ int64_t slab_floats(const WWParams& p) {
 int64_t wino_wgrad_workspace_bytes(const rehr_wgrad_desc& d) {
   WWParams p;
   if (!plan(d, p)) return 0;
-  return (slab_floats(p) + (int64_t)p.splits * p.Capad) * 4 + 64;
+  return need_bytes(p);
 }
 
 // REHR_OK launched, REHR_ENOSUP not applicable
 int wino_wgrad_try(const rehr_wgrad_desc& d, hipStream_t stream) {
   WWParams p;
   if (!plan(d, p)) return REHR_ENOSUP;
-  const int64_t need = (slab_floats(p) + (int64_t)p.splits * p.Capad) * 4 + 64;
-  if (!d.workspace || d.workspace_bytes < need || ((uintptr_t)d.workspace & 15)) return REHR_EINVAL;
+  if (!d.workspace || d.workspace_bytes < need_bytes(p) || ((uintptr_t)d.workspace & 15)) return REHR_EINVAL;
   p.slabs = d.workspace;
   p.slab_bias = d.dbias ? d.workspace + slab_floats(p) : nullptr;
   // (only with many splits in whole groups of 8: with a handful of splits the valid blocks would pile up on a few XCDs)
