@@ -643,6 +643,30 @@ int rehr_stage2_prep_f32(const float* img, const uint32_t* minmax, const float* 
 int rehr_stage2_unc_u8_f32(const float* u, const uint32_t* minmax, uint8_t* out, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Stage-1 volume preparation on the device (utils/sr_utils.py:244-277 postprocess_smore; rehrseg_amd/utils/sr_utils.py
+ * drives it, csrc/stage1_volume.hip).  The cubic B-spline prefilter is ndimage's spline_filter1d(mode='mirror'): gain 6,
+ * pole sqrt(3) - 2, the causal pass started from the exact sum over the mirrored line, carried in fp64 in ndimage's
+ * order of operations; a line of one sample is left as it is.  Lines of up to 283 samples (REHR_ENOSUP above).
+ * ------------------------------------------------------------------------- */
+/* scipy.ndimage.zoom along the slice axis of the stored (lines, n, C) fp32 volume (lines = X * Y), C in {1, 2}:
+ * img[l][j] = fp32(sum_q coeff[l][idx[j][q]] * w[j][q]), q = 0..3 in this order in fp64, coeff = the prefiltered
+ * channel 0; with C == 2 label[l][j] = (uint8)(int32) vol[l][nn[j]][1], 0 where nn[j] < 0.  idx: int32 [Z][4], w: double
+ * [Z][4], nn: int32 [Z] on the device (nn, label: NULL with C == 1); indices are clamped into [0, n).  img: (lines, Z)
+ * fp32, label: (lines, Z) uint8. */
+int rehr_zoom_depth_f32(const float* vol, int64_t lines, int32_t n, int32_t C, const int32_t* idx, const double* w,
+                        const int32_t* nn, int32_t Z, float* img, uint8_t* label, void* stream);
+/* y = the B-spline coefficients of x along the middle axis of its (outer, n, inner) view, rounded to fp32 once; x, y
+ * distinct. */
+int rehr_bspline_prefilter_axis_f64acc_f32(const float* x, float* y, int64_t outer, int32_t n, int64_t inner,
+                                           void* stream);
+/* img: (X, Y, Z) fp32.  axis 0: out (Z, X, Y), out[z][x][y] = sum_t taps[t] * img[x + t - (L - 1) / 2][y][z];
+ * axis 1: out (Z, Y, X), out[z][y][x] = sum_t taps[t] * img[x][y + t - (L - 1) / 2][z]; terms outside the axis are
+ * dropped; one fmaf per tap in tap order from 0 (the bits of rehr_axis_resample_f32 over the blur's tap table).
+ * taps: L <= 32 device floats (REHR_ENOSUP above). */
+int rehr_blur_to_slices_f32(const float* img, const float* taps, int32_t L, float* out, int32_t X, int32_t Y, int32_t Z,
+                            int32_t axis, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mixed-precision (*_bf16) variants of the HBM-bound fused-block kernels: the SAME arguments as the *_f32 entry
  * points above with every ACTIVATION pointer (x, y, res, dy, dx, dres) addressing bf16 elements (ld* in elements,
  * % 8 == 0, C % 8 == 0); gates, gamma / beta, mean_rstd stay fp32, statistics and reduction buffers fp64, the

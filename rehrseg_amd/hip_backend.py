@@ -1216,6 +1216,63 @@ def stage2_unc_u8(u, minmax_codes):
     return out
 
 
+# ----------------------------------------------------------------------------- stage-1 volume preparation (stage1_volume.hip)
+def zoom_depth(vol, idx, w, nn):
+    """scipy.ndimage.zoom along the slice axis of vol (X, Y, n, C) fp32, C in {1, 2}, from the tables of
+    utils.sr_utils.zoom_taps on the device: idx int32 [Z, 4], w float64 [Z, 4], nn int32 [Z].  Returns img (X, Y, Z)
+    fp32 (order 3 of channel 0) and label (X, Y, Z) uint8 (order 0 of channel 1; None with C == 1)
+    (rehr_zoom_depth_f32)."""
+    _chk_eval(vol, torch.float32, "zoom_depth volume", 4)
+    _chk_eval(idx, torch.int32, "zoom_depth idx", 2)
+    _chk_eval(w, torch.float64, "zoom_depth w", 2)
+    _chk_eval(nn, torch.int32, "zoom_depth nn", 1)
+    X, Y, n, Cc = vol.shape
+    Z = idx.shape[0]
+    if Cc not in (1, 2) or X * Y * n == 0 or Z < 1 or tuple(idx.shape) != (Z, 4) or tuple(w.shape) != (Z, 4) or \
+            nn.numel() != Z:
+        raise L.RehrsegHipError(f"zoom_depth: a non-empty (x, y, n, 1 or 2) volume and tables [Z, 4], [Z, 4], [Z], got "
+                                f"{tuple(vol.shape)}, {tuple(idx.shape)}, {tuple(w.shape)}, {tuple(nn.shape)}")
+    img = torch.empty((X, Y, Z), device=vol.device, dtype=torch.float32)
+    label = torch.empty((X, Y, Z), device=vol.device, dtype=torch.uint8) if Cc == 2 else None
+    L.check(L.load().rehr_zoom_depth_f32(_ptr(vol), X * Y, n, Cc, _ptr(idx), _ptr(w), _ptr(nn if Cc == 2 else None), Z,
+                                         _ptr(img), _ptr(label), _stream()), "rehr_zoom_depth_f32")
+    return img, label
+
+
+def bspline_prefilter(x, axis):
+    """The cubic B-spline coefficients of the float32 device tensor x along `axis` (mirror boundaries, fp64 recursion,
+    one rounding to fp32): scipy.ndimage.spline_filter1d(x, 3, axis, mode='mirror')
+    (rehr_bspline_prefilter_axis_f64acc_f32)."""
+    _chk_eval(x, torch.float32, "bspline_prefilter input")
+    if x.dim() < 1 or x.numel() == 0:
+        raise L.RehrsegHipError("bspline_prefilter: a non-empty tensor")
+    axis = axis % x.dim()
+    outer = 1
+    for s in x.shape[:axis]:
+        outer *= s
+    inner = 1
+    for s in x.shape[axis + 1:]:
+        inner *= s
+    y = torch.empty_like(x)
+    L.check(L.load().rehr_bspline_prefilter_axis_f64acc_f32(_ptr(x), _ptr(y), outer, x.shape[axis], inner, _stream()),
+            "rehr_bspline_prefilter_axis_f64acc_f32")
+    return y
+
+
+def blur_to_slices(img, taps, axis):
+    """The blur `taps` (float32 device vector, L <= 32, zero-padded 'same' cross-correlation) of img (X, Y, Z) fp32 along
+    x (axis 0; returns (Z, X, Y)) or y (axis 1; returns (Z, Y, X)) (rehr_blur_to_slices_f32)."""
+    _chk_eval(img, torch.float32, "blur_to_slices img", 3)
+    _chk_eval(taps, torch.float32, "blur_to_slices taps", 1)
+    if axis not in (0, 1) or img.numel() == 0 or taps.numel() == 0:
+        raise L.RehrsegHipError("blur_to_slices: axis 0 (x) or 1 (y) of a non-empty (x, y, z) image")
+    X, Y, Z = img.shape
+    out = torch.empty((Z, X, Y) if axis == 0 else (Z, Y, X), device=img.device, dtype=torch.float32)
+    L.check(L.load().rehr_blur_to_slices_f32(_ptr(img), _ptr(taps), taps.numel(), _ptr(out), X, Y, Z, axis, _stream()),
+            "rehr_blur_to_slices_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- sr_head.2 on the bf16 matrix cores
 def _thin5_ws(d, dev, f32=False):
     fn = L.load().rehr_conv5_thin_f32_workspace_bytes if f32 else L.load().rehr_conv5_thin_workspace_bytes

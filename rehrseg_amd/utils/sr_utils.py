@@ -10,7 +10,14 @@ runs on the device as well: `sr_volume_flavr` feeds the windows straight out of 
 scatters the network's output into the final volumes, `postprocess_flavr_volume` normalises and blurs them, and
 `stage2_volumes` returns what TrainSetMultipleSegSREfficient(volumes=...) consumes without leaving HBM.  The
 reference-named wrappers `inference_flavr` / `postprocess_flavr` take arrays and a dict where the reference takes file
-names (nibabel and SimpleITK are absent)."""
+names (nibabel and SimpleITK are absent).
+
+The step in front of stage 1 (postprocess_smore :244-277, the default path of train_all.py:321-330) runs on the device
+too: `postprocess_smore_volume` zooms the stored volume along its slice axis as scipy.ndimage.zoom does (order 3 for the
+image, order 0 for the label) and blurs the result in-plane, and `stage1_volumes` returns what
+TrainSetMultiple(volumes=...) keeps without an upload."""
+import math
+
 import numpy as np
 import torch
 
@@ -204,3 +211,108 @@ def postprocess_flavr(subject, slice_seperation=4, sr_path=None):
     from .parse_image_file import blur_fwhm_voxels
     kernel = parse_kernel(None, "gaussian", blur_fwhm_voxels(float(slice_seperation), 1.0))
     return postprocess_flavr_volume(sr_path["_img"], sr_path["_seg"], kernel, sr_path.get("_uncertainty"))
+
+
+# ----------------------------------------------------------------------------- stage-1 volume preparation on the device
+_zoom_cache = {}   # (n, separation, device) -> (idx, w, nn) on the device: one table per line length of a run
+
+
+def zoom_taps(n, separation, device=None):
+    """scipy.ndimage.zoom(a, separation, order) along an axis of n samples (mode='constant', grid_mode=False) as tables,
+    computed in Python doubles in ndimage's own order of operations: Z = round(n * separation) output samples, sample j
+    at p = j * ((n - 1) / (Z - 1)) (Z == 1: p = 0).
+
+      idx  int32 [Z, 4]    floor(p) - 1 .. floor(p) + 2, indices outside the axis mirrored about the end samples
+      w    float64 [Z, 4]  the cubic B-spline weights at p - floor(p) (order 3, applied to the prefiltered line)
+      nn   int32 [Z]       floor(p + 0.5) (order 0: half up, not half to even)
+
+    A position that rounding carries beyond n - 1 is outside the axis for ndimage and reads cval = 0: zero weights and
+    nn = -1.  With `device`, the tables as device tensors, cached per (n, separation, device)."""
+    n = int(n)
+    Z = int(round(n * float(separation)))
+    if n < 1 or Z < 1:
+        raise ValueError(f"zoom_taps: {n} samples at separation {separation!r} leave no output sample")
+    if device is not None:
+        key = (n, float(separation), str(device))
+        if key not in _zoom_cache:
+            _zoom_cache[key] = tuple(torch.from_numpy(t).to(device) for t in zoom_taps(n, separation))
+        return _zoom_cache[key]
+    step = (n - 1) / (Z - 1) if Z > 1 else 1.0
+    idx = np.zeros((Z, 4), np.int32)
+    w = np.zeros((Z, 4), np.float64)
+    nn = np.full((Z,), -1, np.int32)
+    period = 2 * n - 2
+
+    def mirror(i):
+        if n == 1:
+            return 0
+        i = abs(i) % period
+        return period - i if i >= n else i
+
+    for j in range(Z):
+        p = j * step
+        if p > n - 1:
+            continue
+        f = math.floor(p)
+        idx[j] = [mirror(f - 1 + q) for q in range(4)]
+        y = p - f
+        t = 1.0 - y
+        w0 = t * t * t / 6.0
+        w1 = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0
+        w2 = (t * t * (t - 2.0) * 3.0 + 4.0) / 6.0
+        w[j] = [w0, w1, w2, 1.0 - w0 - w1 - w2]
+        nn[j] = math.floor(p + 0.5)
+    return idx, w, nn
+
+
+def postprocess_smore_volume(volume, slice_separation, blur_kernel, device=None):
+    """postprocess_smore (ref :244-277, the branch without an SR network) on the device.  `volume` is the merged
+    (x, y, z, 2) array or device tensor (image, label), `blur_kernel` a parse_kernel result; returns device tensors under
+    the reference's names, with Z = round(z * slice_separation):
+
+      img_hr       (x, y, Z, 1) float32  scipy.ndimage.zoom(image, (1, 1, slice_separation), order=3)
+      label_hr     (x, y, Z, 1) uint8    zoom(label, ..., order=0).astype('uint8')
+      image_x_rgb  (Z, 1, x, y) float32  img_hr blurred along x (F.conv2d, padding='same')
+      image_y_rgb  (Z, 1, y, x) float32  img_hr blurred along y
+
+    The unit axes are views.  Nothing here reads device memory from the host.  `device`: where a host array goes (a
+    tensor stays where it is); default cuda."""
+    be = ops.get_backend()
+    if isinstance(volume, torch.Tensor):
+        dev = volume.device if device is None else torch.device(device)
+    else:
+        dev = torch.device("cuda" if device is None else device)
+    vol = _as_device_volume(volume, dev)
+    if vol.dim() != 4 or vol.shape[3] != 2:
+        raise ValueError(f"expected an (x, y, z, 2) volume, got {tuple(vol.shape)}")
+    img, label = be.zoom_depth(vol, *zoom_taps(vol.shape[2], slice_separation, vol.device))
+    taps = _device_taps(blur_kernel, vol.device)
+    return {"img_hr": img.unsqueeze(3), "label_hr": label.unsqueeze(3),
+            "image_x_rgb": be.blur_to_slices(img, taps, 0).unsqueeze(1),
+            "image_y_rgb": be.blur_to_slices(img, taps, 1).unsqueeze(1)}
+
+
+def stage1_volumes(volumes, slice_separation, blur_kernel, device=None):
+    """train_all.py:321-330 for a list of merged (x, y, z, 2) subjects: the dicts TrainSetMultiple(volumes=...) keeps as
+    they are, resident on the device."""
+    return [postprocess_smore_volume(v, slice_separation, blur_kernel, device) for v in volumes]
+
+
+def postprocess_smore(subject, slice_seperation=4, data_path=None, sr_path=None):
+    """The reference's signature (:244) with the merged (x, y, z, 2) array, or a dict subject -> array, for `data_path`;
+    the blur is the Gaussian of parse_kernel at the FWHM parse_image derives from (slice_seperation, 1.0), where the
+    reference asks degrade for 'rf-pulse-slr' (absent; unpinned).  Returns (img_hr, label_hr, image_x_rgb, image_y_rgb)
+    as device tensors."""
+    if sr_path is not None:
+        raise NotImplementedError("postprocess_smore(sr_path=...) reads the output of the 2-D WDSR network "
+                                  "(inference_smore), which is out of scope (SURVEY section 2); pass data_path")
+    _no_files(data_path)
+    if data_path is None:
+        _no_files("")
+    volume = data_path[subject] if isinstance(data_path, dict) else data_path
+    _no_files(volume)
+    from .blur_kernel_ops import parse_kernel
+    from .parse_image_file import blur_fwhm_voxels
+    kernel = parse_kernel(None, "gaussian", blur_fwhm_voxels(float(slice_seperation), 1.0))
+    r = postprocess_smore_volume(volume, float(slice_seperation), kernel)
+    return r["img_hr"], r["label_hr"], r["image_x_rgb"], r["image_y_rgb"]

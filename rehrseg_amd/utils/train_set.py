@@ -471,7 +471,9 @@ class TrainSetMultipleSegSR(_DeviceSet):
 class TrainSetMultiple(_DeviceSet):
     """utils/train_set.py:226-434.  Per subject: img_hr (x, y, z, 1) float, label_hr (x, y, z, 1) uint8 and, with `blur`,
     the in-plane slice-profile blurred copies image_x_rgb (z, 1, x, y) / image_y_rgb (z, 1, y, x) -- read from the
-    merged container, or built here on the device from `volumes=[(x, y, z, 2) arrays]` and `blur_kernel` (:295-318)."""
+    merged container, or built here on the device from `volumes=[(x, y, z, 2) arrays]` and `blur_kernel` (:295-318).
+    A dict whose entries are tensors already on the data set's device (utils/sr_utils.py stage1_volumes) is kept as it
+    is."""
 
     def __init__(self, image_path, split_subjects, slice_thickness, target_thickness, blur_kernel_fpath, blur_kernel_name,
                  patch_size, random_flip, device, preload=True, blur=True, nnunet_transform=False, norm=True, volumes=None,
@@ -494,7 +496,13 @@ class TrainSetMultiple(_DeviceSet):
             names = os.listdir(image_path)
             volumes = [_read_container(os.path.join(image_path, [x for x in names if s in x][0])) for s in split_subjects]
         for s, v in zip(split_subjects, volumes):
-            if isinstance(v, dict):
+            if isinstance(v, dict) and self._resident(v["img_hr"]):
+                # already in HBM (utils/sr_utils.py stage1_volumes): the four tensors stay where they lie
+                img_hr = v["img_hr"].to(torch.float32).contiguous()
+                label_hr = v["label_hr"].to(self.device, torch.uint8).contiguous()
+                fx = v["image_x_rgb"].to(self.device, torch.float32).contiguous() if blur else None
+                fy = v["image_y_rgb"].to(self.device, torch.float32).contiguous() if blur else None
+            elif isinstance(v, dict):
                 img_hr, label_hr = np.asarray(v["img_hr"]), np.asarray(v["label_hr"])
                 fx = _dev(v["image_x_rgb"], self.device, torch.float32) if blur else None
                 fy = _dev(v["image_y_rgb"], self.device, torch.float32) if blur else None
@@ -517,9 +525,13 @@ class TrainSetMultiple(_DeviceSet):
                     fy = _resample(vol, 1, blur_taps(vol.shape[1], k)).permute(2, 1, 0).unsqueeze(1).contiguous()
             print(s, "image shape", tuple(img_hr.shape))
             self.imgs_hr.append(img_hr)
-            self.labels_hr.append(_dev(label_hr, self.device, torch.uint8))
+            self.labels_hr.append(label_hr if torch.is_tensor(label_hr) else _dev(label_hr, self.device, torch.uint8))
             self.imgs_filtered_x.append(fx)
             self.imgs_filtered_y.append(fy)
+
+    def _resident(self, t):
+        return torch.is_tensor(t) and t.device.type == self.device.type and \
+            self.device.index in (None, t.device.index)
 
     def __len__(self):
         return len(self.all_subjects)
