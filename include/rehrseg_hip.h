@@ -667,6 +667,37 @@ int rehr_blur_to_slices_f32(const float* img, const float* taps, int32_t L, floa
                             int32_t axis, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Stage-1 validation on the device (rehrseg_amd/train_steps.py validate_sr, csrc/sr_metrics.hip): the quality of a
+ * predicted image against its target, and of a predicted foreground against its label, in one pass.
+ * pred / target (and, both or neither, seg_logits / seg_target) are logical (N, D, H, W) images, each addressed by
+ * a base pointer and four element strides (>= 0; any layout, nothing is copied).  pred and seg_logits are fp32
+ * (_f32) or bf16 widened at the load (_bf16); the targets are fp32.  stats[n][7] double, written (not accumulated):
+ *   [0] sum |p - t|   [1] sum (p - t)^2   over the sample's D * H * W voxels
+ *   [2] the sum of the SSIM index (Wang et al. 2004) over all valid window positions of the D slices: per (H, W)
+ *       slice, 11x11 Gaussian window, sigma 1.5, unit sum, separable; the biased window-weighted variances
+ *       E[x^2] - mu_x^2 and covariance; C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ *       S = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_xx + s_yy + C2)); a position is valid when its
+ *       window lies inside the slice
+ *   [3] their number D * (H - 10) * (W - 10)
+ *   [4] #(logit > 0 and target > 0.5)   [5] #(logit > 0)   [6] #(target > 0.5)   (exact; zeros without the pair)
+ * Per-voxel terms and window moments are fp32, every sum over voxels, positions and blocks fp64 in a fixed order:
+ * the same bits on every run; identical pred and target give an index of exactly 1.
+ * H, W >= 11 (REHR_ENOSUP below).  workspace: rehr_sr_metrics_workspace_bytes(N, D, H, W) bytes of device scratch,
+ * 8-byte aligned (< 0: REHR_E*).
+ * ------------------------------------------------------------------------- */
+int64_t rehr_sr_metrics_workspace_bytes(int32_t N, int32_t D, int32_t H, int32_t W);
+int rehr_sr_metrics_f32(const float* pred, const int64_t* pred_strides, const float* target,
+                        const int64_t* target_strides, const float* seg_logits, const int64_t* seg_logits_strides,
+                        const float* seg_target, const int64_t* seg_target_strides, int32_t N, int32_t D, int32_t H,
+                        int32_t W, float data_range, double* stats, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int rehr_sr_metrics_bf16(const void* pred, const int64_t* pred_strides, const float* target,
+                         const int64_t* target_strides, const void* seg_logits, const int64_t* seg_logits_strides,
+                         const float* seg_target, const int64_t* seg_target_strides, int32_t N, int32_t D, int32_t H,
+                         int32_t W, float data_range, double* stats, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mixed-precision (*_bf16) variants of the HBM-bound fused-block kernels: the SAME arguments as the *_f32 entry
  * points above with every ACTIVATION pointer (x, y, res, dy, dx, dres) addressing bf16 elements (ld* in elements,
  * % 8 == 0, C % 8 == 0); gates, gamma / beta, mean_rstd stay fp32, statistics and reduction buffers fp64, the

@@ -1273,6 +1273,46 @@ def blur_to_slices(img, taps, axis):
     return out
 
 
+# ----------------------------------------------------------------------------- stage-1 validation (sr_metrics.hip)
+def sr_metrics(pred, target, seg_logits=None, seg_target=None, data_range=1.0):
+    """Per-sample quality sums of the (N, D, H, W) views pred (fp32 or bf16) against target (fp32), and of the foreground
+    seg_logits > 0 (pred's dtype) against seg_target > 0.5 (fp32): an (N, 7) float64 device tensor {sum |p - t|,
+    sum (p - t)^2, sum of the SSIM index over the valid 11x11 windows of every slice, their number, intersection,
+    predicted and target foreground counts}.  The views are read through their strides, nothing is copied and nothing
+    is read back (rehr_sr_metrics_f32 / _bf16)."""
+    if (seg_logits is None) != (seg_target is None):
+        raise L.RehrsegHipError("sr_metrics: seg_logits and seg_target come together")
+    for t, what in ((pred, "pred"), (target, "target"), (seg_logits, "seg_logits"), (seg_target, "seg_target")):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.RehrsegHipError(f"sr_metrics {what}: a device tensor (no CPU fallback)")
+        if t.dim() != 4 or tuple(t.shape) != tuple(pred.shape):
+            raise L.RehrsegHipError(f"sr_metrics {what}: an (N, D, H, W) view of the prediction's shape "
+                                    f"{tuple(pred.shape)}, got {tuple(t.shape)}")
+        if t.device != pred.device:
+            raise L.RehrsegHipError("sr_metrics: operands on one device")
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise L.RehrsegHipError(f"sr_metrics pred: float32 or bfloat16, got {pred.dtype}")
+    if target.dtype != torch.float32 or (seg_target is not None and seg_target.dtype != torch.float32):
+        raise L.RehrsegHipError("sr_metrics: the targets are float32")
+    if seg_logits is not None and seg_logits.dtype != pred.dtype:
+        raise L.RehrsegHipError("sr_metrics seg_logits: the prediction's dtype")
+    N, D, H, W = (int(v) for v in pred.shape)
+    lib = L.load()
+    nbytes = int(lib.rehr_sr_metrics_workspace_bytes(N, D, H, W))
+    if nbytes < 0:
+        L.check(nbytes, "rehr_sr_metrics_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=pred.device)
+    stats = torch.empty((N, 7), dtype=torch.float64, device=pred.device)
+    strides = lambda t: (C.c_int64 * 4)(*t.stride()) if t is not None else None  # noqa: E731
+    fn, name = _fn("rehr_sr_metrics", pred)
+    L.check(fn(_ptr(pred), strides(pred), _ptr(target), strides(target), _ptr(seg_logits), strides(seg_logits),
+               _ptr(seg_target), strides(seg_target), N, D, H, W, float(data_range), _ptr(stats), _ptr(ws), nbytes,
+               _stream()), name)
+    return stats
+
+
 # ----------------------------------------------------------------------------- sr_head.2 on the bf16 matrix cores
 def _thin5_ws(d, dev, f32=False):
     fn = L.load().rehr_conv5_thin_f32_workspace_bytes if f32 else L.load().rehr_conv5_thin_workspace_bytes

@@ -189,6 +189,9 @@ PROTOTYPES = {
     "rehr_zoom_depth_f32": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "rehr_bspline_prefilter_axis_f64acc_f32": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp]),
     "rehr_blur_to_slices_f32": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "rehr_sr_metrics_workspace_bytes": (_i64, [_i32] * 4),
+    "rehr_sr_metrics_f32": (C.c_int, [_vp] * 8 + [_i32] * 4 + [_f32, _vp, _vp, _i64, _vp]),
+    "rehr_sr_metrics_bf16": (C.c_int, [_vp] * 8 + [_i32] * 4 + [_f32, _vp, _vp, _i64, _vp]),
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),

@@ -3,6 +3,7 @@ pass, on the MI355X modules.
 
   get_intermediate_features   train_all.py:85-112   (teacher features for distillation)
   train_sr_step               train_all.py:118-139  (stage 1b/1c: FLAVR self-SR step)
+  validate_sr                 (no counterpart)      (stage-1 validation on held-out LR / HR pairs, on the device)
   train_segsr_step            train_all.py:521-556  (stage 2: SegModel + distillation step)
   evaluate / evaluate_cases   train_all.py:154-193  (stage-2 validation, evaluate_case on the device)
 
@@ -96,6 +97,53 @@ def train_sr_step(model, opt, scheduler, patches_lr, patches_hr, loss_obj, loss_
     if scheduler is not None:
         scheduler.step()
     return loss
+
+
+def validate_sr(model, data_set, n_batches, batch_size, slice_separation, num_slices, enable_uncertainty=False,
+                data_range=1.0, seed=0):
+    """Stage-1 validation (the reference has none): the (patches_lr, patches_hr) pairs TrainSetMultiple builds from
+    held-out subjects have known truth, so the network's channel 0 is scored against the HR image (L1, MSE, PSNR, SSIM
+    per slice) and its channel 1 against the HR label (Dice), on the device (ops backend sr_metrics).  Returns
+    utils.sr_utils.sr_quality's dict over the n_batches * batch_size samples.
+
+    Batch b holds the items (b * batch_size + j) % len(data_set), j = 0 .. batch_size - 1, drawn from Python's `random`
+    seeded with `seed`; the generator's state is saved first and restored on exit (also on an exception), so a training
+    loop's draws are untouched.  patches_hr is cut to the middle slice_separation slices as train_sr_step does.  The
+    model runs in eval() under no_grad in the caller's precision mode (its previous mode is restored) and its output is
+    read where it lies, in the dtype it comes in.  The stats stay on the device until the one host read at the end."""
+    import random
+
+    from . import ops
+    from .utils.sr_utils import sr_quality
+    if getattr(data_set, "train_transform", None) is not None:
+        raise ValueError("validate_sr: a data set with train_transform set yields augmented patches (and draws from "
+                         "other generators); build the validation set without it")
+    n_batches, batch_size = int(n_batches), int(batch_size)
+    if n_batches < 1 or batch_size < 1 or len(data_set) < 1:
+        raise ValueError("validate_sr needs at least one batch of at least one item of a non-empty data set")
+    be = ops.get_backend()
+    state = random.getstate()
+    was_training = model.training
+    stats, voxels = [], None
+    try:
+        random.seed(seed)
+        model.eval()
+        with torch.no_grad():
+            for b in range(n_batches):
+                patches_lr, patches_hr = data_set.batch([(b * batch_size + j) % len(data_set)
+                                                         for j in range(batch_size)])
+                if num_slices > 1:
+                    s = int(slice_separation)
+                    patches_hr = patches_hr[:, :, s * (num_slices // 2 - 1):s * (num_slices // 2), ...]
+                hat = model(patches_lr)
+                if enable_uncertainty:
+                    hat = hat[0]
+                stats.append(be.sr_metrics(hat[:, 0], patches_hr[:, 0], hat[:, 1], patches_hr[:, 1], data_range))
+                voxels = hat[0, 0].numel()
+    finally:
+        model.train(was_training)
+        random.setstate(state)
+    return sr_quality(torch.cat(stats, 0), voxels, data_range)
 
 
 _TEACHER_STREAMS = {}

@@ -316,3 +316,22 @@ def postprocess_smore(subject, slice_seperation=4, data_path=None, sr_path=None)
     kernel = parse_kernel(None, "gaussian", blur_fwhm_voxels(float(slice_seperation), 1.0))
     r = postprocess_smore_volume(volume, float(slice_seperation), kernel)
     return r["img_hr"], r["label_hr"], r["image_x_rgb"], r["image_y_rgb"]
+
+
+# ----------------------------------------------------------------------------- stage-1 validation
+def sr_quality(stats, voxels_per_sample, data_range=1.0):
+    """The quality numbers of accumulated (n, 7) sr_metrics stats (one row per validation sample) as Python numbers:
+    l1, mse and ssim are means over the samples, psnr the mean of 10 log10(data_range^2 / mse_n) (inf where a sample's
+    mse is 0), dice the Dice of the summed exact counts (calculate_dice's smoothing, 1e-5), n the number of samples.
+    The one place that reads the stats on the host."""
+    from .seg_utils import _dice_from_counts
+    s = stats.detach().to("cpu", torch.float64).numpy().reshape(-1, 7)
+    if s.shape[0] == 0:
+        raise ValueError("sr_quality needs the stats of at least one sample")
+    mse = s[:, 1] / float(voxels_per_sample)
+    with np.errstate(divide="ignore"):
+        psnr = 10.0 * np.log10(float(data_range) ** 2 / mse)
+    inter, n_pred, n_tgt = (int(round(float(v))) for v in s[:, 4:7].sum(0))
+    return {"l1": float((s[:, 0] / float(voxels_per_sample)).mean()), "mse": float(mse.mean()),
+            "psnr": float(psnr.mean()), "ssim": float((s[:, 2] / s[:, 3]).mean()),
+            "dice": float(_dice_from_counts(inter, n_pred, n_tgt)), "n": int(s.shape[0])}
