@@ -280,6 +280,11 @@ int64_t rehr_conv_small_cin_wgrad_workspace_bytes(const rehr_direct_conv_desc* d
 /* 1 when rehr_conv_small_cin_wgrad_f32 takes this shape on the matrix cores (thin_cin_conv.hip: C_out 32 / 64,
  * 1x3x3 / 3x3x3 / (3,7,7) taps, stride_w <= 2) -- dY and x are then each read once, no im2col columns */
 int rehr_conv_small_cin_wgrad_on_mfma(const rehr_direct_conv_desc* d);
+/* 1 when rehr_conv_small_cin_fwd_f32 takes this shape on the matrix cores, which is when rehr_conv_small_cin_fwd_ybf16
+ * takes it at all (C_out 32 / 64, kW <= 8, stride_w <= 2, weights and patch within 150 KB of LDS).  A question about
+ * the shape, to be asked before y is allocated: x, w and y may be null; a y that is given is held to the alignment of
+ * bf16 elements (8 bytes).  (ABI 6) */
+int rehr_conv_small_cin_fwd_on_mfma(const rehr_direct_conv_desc* d);
 /* Mixed precision: the same layers with y (forward) / dY (weight gradient) pointing at bf16 elements -- the thin-input
  * layers compute in fp32 on the fp32 image, the layer behind takes bf16.  Matrix-core shapes only
  * (rehr_conv_small_cin_wgrad_on_mfma; C_out 32 / 64, kW <= 8, stride_w <= 2 for the forward), else REHR_ENOSUP.

@@ -2,7 +2,7 @@
 // almost no arithmetic per byte (Cin in {1,2} or Cout <= 4), so they are written
 // for the HBM roofline: NDHWC, 16-byte stores, weights staged once per block in
 // LDS and read with wave-uniform (broadcast) addresses.
-#include "common.h"
+#include "direct_shared.h"
 #include <cstdlib>
 
 namespace {
@@ -187,43 +187,35 @@ __global__ void small_cin_wgrad_reduce_kernel(const float* __restrict__ slab, in
   }
 }
 
-bool small_cin_ok(const rehr_direct_conv_desc& d) {
-  if (!d.x || !d.w || !d.y) return false;
+// what the thin-input entry points ask of the shape ...
+bool small_cin_shape_ok(const rehr_direct_conv_desc& d) {
   if (d.Cin < 1 || d.Cin > 2) return false;
   if (d.Cout != 16 && d.Cout != 32 && d.Cout != 64) return false;
-  if (d.ldy % 4 || (((uintptr_t)d.y) & 15)) return false;
-  if (d.N < 1 || d.N > 65535) return false;
-  if (d.KD < 1 || d.KH < 1 || d.KW < 1 || d.sd < 1 || d.sh < 1 || d.sw < 1) return false;
-  // output extent must follow from the input extent
-  if ((d.Di + 2 * d.pd - d.KD) / d.sd + 1 != d.Do) return false;
-  if ((d.Hi + 2 * d.ph - d.KH) / d.sh + 1 != d.Ho) return false;
-  if ((d.Wi + 2 * d.pw - d.KW) / d.sw + 1 != d.Wo) return false;
-  return true;
+  if (d.ldy % 4 || d.N < 1 || d.N > 65535) return false;
+  return d.KD >= 1 && d.KH >= 1 && d.KW >= 1 && conv_out_extent_ok(d);
+}
+// ... and of the pointers (y: fp32 elements)
+bool small_cin_ok(const rehr_direct_conv_desc& d) {
+  return d.x && d.w && d.y && !(((uintptr_t)d.y) & 15) && small_cin_shape_ok(d);
 }
 
-int wgrad_blocks(const rehr_direct_conv_desc& d, int64_t* vpb) {
+// slabs of the vector weight gradient: [blocks][Cin*T + 1][64] floats
+int64_t small_cin_wgrad_plan(const rehr_direct_conv_desc& d, int& blocks, int64_t& vox_per_block) {
   const int64_t total = (int64_t)d.N * d.Do * d.Ho * d.Wo;
-  int64_t blocks = 1024;
-  int64_t per = (total + blocks - 1) / blocks;
-  if (per < 64) per = 64;
-  blocks = (total + per - 1) / per;
-  *vpb = per;
-  return (int)blocks;
+  vox_per_block = (total + 1023) / 1024;
+  if (vox_per_block < 64) vox_per_block = 64;
+  blocks = (int)((total + vox_per_block - 1) / vox_per_block);
+  return (int64_t)blocks * ((int64_t)d.Cin * d.KD * d.KH * d.KW + 1) * 64 * sizeof(float);
 }
 
 }  // namespace
-
-int thin_cin_fwd_try(const rehr_direct_conv_desc& d, hipStream_t stream, bool y_bf16);   // thin_cin_conv.hip: fp32 matrix cores
-int64_t thin_cin_wgrad_workspace_bytes(const rehr_direct_conv_desc& d);
-int thin_cin_wgrad_try(const rehr_direct_conv_desc& d, float* dw, float* dbias, float* workspace, int64_t workspace_bytes,
-                       hipStream_t stream, bool dy_bf16);
 
 extern "C" int rehr_conv_small_cin_fwd_f32(const rehr_direct_conv_desc* dp, void* stream) {
   if (!dp || !small_cin_ok(*dp)) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
   if (d.stats_mode != 0 && !d.stats) return REHR_EINVAL;
   {
-    const int rc = thin_cin_fwd_try(d, (hipStream_t)stream, false);   // C_out 32 / 64, kW <= 8, stride_w <= 2
+    const int rc = thin_cin_fwd_launch(d, (hipStream_t)stream, false);   // C_out 32 / 64, kW <= 8, stride_w <= 2
     if (rc != REHR_ENOSUP) return rc;
   }
   const int T = d.KD * d.KH * d.KW;
@@ -263,10 +255,9 @@ extern "C" int rehr_conv_small_cin_wgrad_f32(const rehr_direct_conv_desc* dp, fl
     if (rc != REHR_ENOSUP) return rc;
   }
   const int T = d.KD * d.KH * d.KW;
+  int blocks;
   int64_t vpb;
-  const int blocks = wgrad_blocks(d, &vpb);
-  const int64_t need = (int64_t)blocks * ((int64_t)d.Cin * T + 1) * 64 * sizeof(float);
-  if (workspace_bytes < need) return REHR_EINVAL;
+  if (workspace_bytes < small_cin_wgrad_plan(d, blocks, vpb)) return REHR_EINVAL;
   const int tpw = (T + 3) / 4;
   hipStream_t st = (hipStream_t)stream;
   if (tpw <= 8)
@@ -287,7 +278,7 @@ extern "C" int rehr_conv_small_cin_wgrad_f32(const rehr_direct_conv_desc* dp, fl
 extern "C" int rehr_conv_small_cin_fwd_ybf16(const rehr_direct_conv_desc* dp, void* stream) {
   if (!dp || !dp->x || !dp->w || !dp->y) return REHR_EINVAL;
   if (dp->stats_mode != 0 && !dp->stats) return REHR_EINVAL;
-  return thin_cin_fwd_try(*dp, (hipStream_t)stream, true);
+  return thin_cin_fwd_launch(*dp, (hipStream_t)stream, true);
 }
 extern "C" int rehr_conv_small_cin_wgrad_dybf16(const rehr_direct_conv_desc* dp, float* dw, float* dbias,
                                                 float* workspace, int64_t workspace_bytes, void* stream) {
@@ -298,6 +289,10 @@ extern "C" int rehr_conv_small_cin_wgrad_dybf16(const rehr_direct_conv_desc* dp,
 extern "C" int rehr_conv_small_cin_wgrad_on_mfma(const rehr_direct_conv_desc* dp) {
   return dp && small_cin_ok(*dp) && thin_cin_wgrad_workspace_bytes(*dp) > 0;
 }
+// asked before y exists: the shape, and the address only when there is one (bf16 elements, as rehr_conv_small_cin_fwd_ybf16)
+extern "C" int rehr_conv_small_cin_fwd_on_mfma(const rehr_direct_conv_desc* dp) {
+  return dp && small_cin_shape_ok(*dp) && !(((uintptr_t)dp->y) & 7) && thin_cin_fwd_has_plan(*dp);
+}
 
 extern "C" int64_t rehr_conv_small_cin_wgrad_workspace_bytes(const rehr_direct_conv_desc* dp) {
   if (!dp) return REHR_EINVAL;
@@ -305,10 +300,9 @@ extern "C" int64_t rehr_conv_small_cin_wgrad_workspace_bytes(const rehr_direct_c
     const int64_t b = small_cin_ok(*dp) ? thin_cin_wgrad_workspace_bytes(*dp) : 0;
     if (b > 0) return b;
   }
+  int blocks;
   int64_t vpb;
-  const int blocks = wgrad_blocks(*dp, &vpb);
-  const int T = dp->KD * dp->KH * dp->KW;
-  return (int64_t)blocks * ((int64_t)dp->Cin * T + 1) * 64 * sizeof(float);
+  return small_cin_wgrad_plan(*dp, blocks, vpb);
 }
 
 // ------------------------------------------------------------------ im2col for thin inputs
@@ -367,9 +361,7 @@ extern "C" int rehr_im2col_f32(const rehr_direct_conv_desc* dp, float* out, int3
   if (!d.x || d.Cin < 1 || d.Cin > 127 || d.N < 1) return REHR_EINVAL;
   if (d.KD < 1 || d.KH < 1 || d.KW < 1 || d.KD > 255 || d.KH > 255 || d.KW > 255) return REHR_EINVAL;
   if (Kpad % 4 || Kpad < d.Cin * d.KD * d.KH * d.KW || (((uintptr_t)out) & 15)) return REHR_EINVAL;
-  if ((d.Di + 2 * d.pd - d.KD) / d.sd + 1 != d.Do || (d.Hi + 2 * d.ph - d.KH) / d.sh + 1 != d.Ho ||
-      (d.Wi + 2 * d.pw - d.KW) / d.sw + 1 != d.Wo)
-    return REHR_EINVAL;
+  if (!conv_out_extent_ok(d)) return REHR_EINVAL;
   const size_t smem = (size_t)Kpad * sizeof(int);
   if (smem > 48 * 1024) return REHR_ENOSUP;
   const int64_t total = (int64_t)d.N * d.Do * d.Ho * d.Wo * (Kpad / 4);
@@ -1087,10 +1079,7 @@ bool small_cout_ok(const rehr_direct_conv_desc& d) {
   if (d.sd != 1 || d.sh != 1 || d.sw != 1) return false;
   if (d.KD < 1 || d.KH < 1 || d.KW < 1 || d.KW > SC_MAXKW) return false;
   if (d.ldx % 4 || (((uintptr_t)d.x) & 15)) return false;
-  if (d.N < 1) return false;
-  if (d.Di + 2 * d.pd - d.KD + 1 != d.Do || d.Hi + 2 * d.ph - d.KH + 1 != d.Ho || d.Wi + 2 * d.pw - d.KW + 1 != d.Wo)
-    return false;
-  return true;
+  return d.N >= 1 && conv_out_extent_ok(d);
 }
 bool sc_cg(const rehr_direct_conv_desc& d) { return d.Cin == 16 || d.Cin == 32 || d.Cin == 64; }
 bool sc_halo(const rehr_direct_conv_desc& d) {
@@ -1106,6 +1095,11 @@ int sc_halo_blocks(const rehr_direct_conv_desc& d, int* bpb, int* nbd, int* nbh,
   blocks = (nbricks + per - 1) / per;
   *bpb = (int)per;
   return (int)blocks;
+}
+int64_t sc_weights(const rehr_direct_conv_desc& d) { return (int64_t)d.Cout * d.Cin * d.KD * d.KH * d.KW; }
+// workspace of the weight gradient: [strips][Cout][Cin][T] partial sums, then [SC_BIAS_BLOCKS][4] bias partials
+int64_t sc_wgrad_bytes(const rehr_direct_conv_desc& d, int strips) {
+  return ((int64_t)strips * sc_weights(d) + SC_BIAS_BLOCKS * 4) * (int64_t)sizeof(float);
 }
 int sc_strips(const rehr_direct_conv_desc& d, int* rpb) {
   if (sc_halo(d)) { int a, b, c; return sc_halo_blocks(d, rpb, &a, &b, &c); }
@@ -1170,8 +1164,7 @@ extern "C" int rehr_conv_small_cout_dgrad_f32(const rehr_direct_conv_desc* dp, f
 extern "C" int64_t rehr_conv_small_cout_wgrad_workspace_bytes(const rehr_direct_conv_desc* dp) {
   if (!dp || !small_cout_ok(*dp)) return REHR_EINVAL;
   int rpb;
-  const int strips = sc_strips(*dp, &rpb);
-  return ((int64_t)strips * dp->Cout * dp->Cin * dp->KD * dp->KH * dp->KW + SC_BIAS_BLOCKS * 4) * sizeof(float);
+  return sc_wgrad_bytes(*dp, sc_strips(*dp, &rpb));
 }
 
 extern "C" int rehr_conv_small_cout_wgrad_f32(const rehr_direct_conv_desc* dp, float* dw, float* dbias,
@@ -1180,8 +1173,8 @@ extern "C" int rehr_conv_small_cout_wgrad_f32(const rehr_direct_conv_desc* dp, f
   const rehr_direct_conv_desc& d = *dp;
   int rpb;
   const int strips = sc_strips(d, &rpb);
-  const int64_t nw = (int64_t)d.Cout * d.Cin * d.KD * d.KH * d.KW;
-  if (workspace_bytes < ((int64_t)strips * nw + SC_BIAS_BLOCKS * 4) * (int64_t)sizeof(float)) return REHR_EINVAL;
+  const int64_t nw = sc_weights(d);
+  if (workspace_bytes < sc_wgrad_bytes(d, strips)) return REHR_EINVAL;
   float* bpart = workspace + (int64_t)strips * nw;
   const int CO = d.Cout <= 2 ? 2 : 4;
   const int64_t blocks = (int64_t)strips * d.KD * d.KH * (d.Cin / 4);
@@ -1219,6 +1212,53 @@ extern "C" int rehr_conv_small_cout_wgrad_f32(const rehr_direct_conv_desc* dp, f
                        (int64_t)d.N * d.Do * d.Ho * d.Wo, bpart);
   hipLaunchKernelGGL(small_cout_wgrad_reduce_kernel, dim3((unsigned)((nw + 15) / 16)), dim3(256), 0, st, workspace,
                      strips, nw, dw, bpart, SC_BIAS_BLOCKS, d.Cout, dbias);
+  REHR_LAUNCH_CHECK();
+  return REHR_OK;
+}
+
+// ------------------------------------------------------------------ sr_head.2 on the matrix cores: the reduction
+// that the weight gradients of thin_conv_bf16.hip and thin_conv_f32.hip share
+namespace {
+// dw (2,16,5,5,5) = sum over block slabs, fixed order; slab index [(kd*5 + kw)][ci][kh*2 + co]
+// 8 threads share an output element (thread (e, g) sums the blocks g, g + 8, ...; fixed-order combine through LDS): one
+// thread per element walking every block's slab was a 0.29 ms latency chain at 160^3
+__global__ __launch_bounds__(256) void thin5_wgrad_reduce_kernel(const float* __restrict__ slabs, int nblocks, float* __restrict__ dw,
+                                                             float* __restrict__ dbias) {
+  constexpr int G = 8, EPB = 256 / G, NDW = 2 * T5_CIN * 125;
+  __shared__ float part[256];
+  const int el = threadIdx.x % EPB, g = threadIdx.x / EPB;
+  const int i = blockIdx.x * EPB + el;   // index into dw (2,16,5,5,5), then the two bias gradients
+  int si = -1;
+  if (i < NDW) {
+    const int kw = i % 5, kh = (i / 5) % 5, kd = (i / 25) % 5, ci = (i / 125) % T5_CIN, co = i / (125 * T5_CIN);
+    si = ((kd * 5 + kw) * 16 + ci) * 16 + kh * 2 + co;
+  } else if (i < NDW + 2) {
+    si = T5_SLAB + (i - NDW);
+  }
+  float s0 = 0.f, s1 = 0.f;
+  if (si >= 0) {
+    int bq = g;
+    for (; bq + G < nblocks; bq += 2 * G) {
+      s0 += slabs[(int64_t)bq * T5_SLABF + si];
+      s1 += slabs[(int64_t)(bq + G) * T5_SLABF + si];
+    }
+    for (; bq < nblocks; bq += G) s0 += slabs[(int64_t)bq * T5_SLABF + si];
+  }
+  part[threadIdx.x] = s0 + s1;
+  __syncthreads();
+  if (g == 0 && si >= 0) {
+    float s = part[el];
+#pragma unroll
+    for (int q = 1; q < G; ++q) s += part[q * EPB + el];
+    if (i < NDW) dw[i] = s;
+    else if (dbias != nullptr) dbias[i - NDW] = s;
+  }
+}
+}  // namespace
+
+int thin5_wgrad_reduce(const float* slabs, int nblocks, float* dw, float* dbias, hipStream_t st) {
+  hipLaunchKernelGGL(thin5_wgrad_reduce_kernel, dim3((2 * T5_CIN * 125 + 2 + 31) / 32), dim3(256), 0, st, slabs, nblocks,
+                     dw, dbias);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }

@@ -13,7 +13,7 @@
 // ([k step][kq][c_out], loaded once per block; blocks walk several tiles), every A dword feeds NV voxel tiles and every
 // B dword all c_out tiles.  M = c_out makes the accumulator quad of a lane 4 consecutive channels of one voxel: 16-byte
 // NDHWC stores.  Epilogue: bias, activation, fp64 statistics of the stored values (one atomic per channel and block).
-#include "common.h"
+#include "direct_shared.h"
 
 namespace {
 
@@ -165,19 +165,13 @@ __global__ __launch_bounds__(256) void thin_cin_fwd_kernel(const ThinCinParams p
   }
 }
 
-}  // namespace
-
-// rehr_conv_small_cin_fwd_f32 tries this first; REHR_ENOSUP = not a shape for it
-// y_bf16: d.y points at bf16 elements (mixed precision: the layer behind takes bf16 activations)
-int thin_cin_fwd_try(const rehr_direct_conv_desc& d, hipStream_t stream, bool y_bf16) {
-  if (d.Cin < 1 || d.Cin > 2 || (d.Cout != 32 && d.Cout != 64) || d.KW > 8 || d.sw < 1 || d.sw > 2 || d.ldy % 4 ||
-      (reinterpret_cast<uintptr_t>(d.y) & (y_bf16 ? 7 : 15)))
-    return REHR_ENOSUP;
-  ThinCinParams p;
+bool thin_cin_fwd_plan(const rehr_direct_conv_desc& d, ThinCinParams& p, dim3& grid, size_t& smem) {
+  if (d.Cin < 1 || d.Cin > 2 || (d.Cout != 32 && d.Cout != 64) || d.KW > 8 || d.sw < 1 || d.sw > 2 || d.ldy % 4)
+    return false;
   p.d = d;
   p.G = (d.KW + 3) / 4;
   p.ksteps = d.Cin * d.KD * d.KH * p.G;
-  const int NTN = d.Cout / 16, NV = d.Cout == 32 ? 4 : 2, COLS = 16 * NV;
+  const int COLS = d.Cout == 32 ? 64 : 32;
   p.PH = 3 * d.sh + d.KH;
   p.PW = (COLS - 1) * d.sw + 4 * p.G;
   p.PW += (p.PW & 1) ? 0 : 1;                       // odd row pitch
@@ -185,12 +179,12 @@ int thin_cin_fwd_try(const rehr_direct_conv_desc& d, hipStream_t stream, bool y_
   size_t pbytes = (size_t)d.Cin * d.KD * p.PH * p.PW * sizeof(float);
   const size_t rbytes = (size_t)4 * 2 * d.Cout * sizeof(float);
   if (pbytes < rbytes) pbytes = rbytes;
-  const size_t smem = wbytes + pbytes;
-  if (smem > 150 * 1024) return REHR_ENOSUP;
+  smem = wbytes + pbytes;
+  if (smem > 150 * 1024) return false;
   p.tiles_h = (d.Ho + 3) / 4;
   p.tiles_w = (d.Wo + COLS - 1) / COLS;
   const int64_t tpi = (int64_t)d.Do * p.tiles_h * p.tiles_w;
-  if (tpi >= ((int64_t)1 << 31)) return REHR_ENOSUP;
+  if (tpi >= ((int64_t)1 << 31)) return false;
   p.tiles_per_img = (int)tpi;
   // blocks walk runs of tiles: the weights are loaded once per block, statistics cost one atomic per channel and block
   int64_t bx = tpi;
@@ -198,7 +192,27 @@ int thin_cin_fwd_try(const rehr_direct_conv_desc& d, hipStream_t stream, bool y_
   if (bx > cap) bx = cap;
   p.tiles_per_block = (int)((tpi + bx - 1) / bx);
   bx = (tpi + p.tiles_per_block - 1) / p.tiles_per_block;
-  dim3 grid((unsigned)bx, d.N);
+  grid = dim3((unsigned)bx, d.N);
+  return true;
+}
+
+}  // namespace
+
+bool thin_cin_fwd_has_plan(const rehr_direct_conv_desc& d) {
+  ThinCinParams p;
+  dim3 grid;
+  size_t smem;
+  return thin_cin_fwd_plan(d, p, grid, smem);
+}
+
+// rehr_conv_small_cin_fwd_f32 tries this first
+// y_bf16: d.y points at bf16 elements (mixed precision: the layer behind takes bf16 activations)
+int thin_cin_fwd_launch(const rehr_direct_conv_desc& d, hipStream_t stream, bool y_bf16) {
+  ThinCinParams p;
+  dim3 grid;
+  size_t smem;
+  if (!thin_cin_fwd_plan(d, p, grid, smem) || (reinterpret_cast<uintptr_t>(d.y) & (y_bf16 ? 7 : 15))) return REHR_ENOSUP;
+  const int NTN = d.Cout / 16;
 #define TCI_LAUNCH(NTN_, NV_, TO_)                                                                                   \
   do {                                                                                                               \
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(thin_cin_fwd_kernel<NTN_, NV_, TO_>),                      \
@@ -430,6 +444,9 @@ bool thin_cin_wgrad_plan(const rehr_direct_conv_desc& d, ThinCinWgParams& p, dim
   grid = dim3((unsigned)bx, d.N, d.Cin);
   return true;
 }
+int64_t thin_cin_wgrad_slab_bytes(const rehr_direct_conv_desc& d, const ThinCinWgParams& p, const dim3& grid) {
+  return (int64_t)grid.x * grid.y * grid.z * d.Cout * p.NTP * (int64_t)sizeof(float);
+}
 
 }  // namespace
 
@@ -437,8 +454,7 @@ int64_t thin_cin_wgrad_workspace_bytes(const rehr_direct_conv_desc& d) {
   ThinCinWgParams p;
   dim3 grid;
   size_t smem;
-  if (!thin_cin_wgrad_plan(d, p, grid, smem)) return 0;
-  return (int64_t)grid.x * grid.y * grid.z * d.Cout * p.NTP * (int64_t)sizeof(float);
+  return thin_cin_wgrad_plan(d, p, grid, smem) ? thin_cin_wgrad_slab_bytes(d, p, grid) : 0;
 }
 
 // rehr_conv_small_cin_wgrad_f32 tries this first; REHR_ENOSUP = not a shape for it
@@ -449,8 +465,8 @@ int thin_cin_wgrad_try(const rehr_direct_conv_desc& d, float* dw, float* dbias, 
   size_t smem;
   if (!thin_cin_wgrad_plan(d, p, grid, smem)) return REHR_ENOSUP;
   if (!dy_bf16 && (reinterpret_cast<uintptr_t>(d.y) & 15)) return REHR_ENOSUP;
-  const int64_t need = (int64_t)grid.x * grid.y * grid.z * d.Cout * p.NTP * (int64_t)sizeof(float);
-  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15)) return REHR_EINVAL;
+  if (!workspace || workspace_bytes < thin_cin_wgrad_slab_bytes(d, p, grid) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+    return REHR_EINVAL;
   p.slabs = workspace;
   p.want_bias = dbias != nullptr;
   const int ntm = d.Cout / 16, ntn = p.NTP / 16;

@@ -14,8 +14,7 @@
 // it touches (kd = 0..4), whose accumulators (5 planes x W/16 tiles x 4 registers) rotate through a five-phase
 // unrolled loop.  All 15 weight fragments stay in registers.  A finished plane's P goes through a per-wave LDS row
 // for the shift-add over kw and leaves as 8 bytes per voxel.
-#include "common.h"
-#include <type_traits>
+#include "direct_shared.h"
 
 namespace {
 
@@ -25,10 +24,7 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int TC_CIN = 16, TC_K = 5, TC_BH = 4;   // channels, kernel extent, output rows per block (= waves)
-constexpr int TC_ROWS = TC_BH + TC_K - 1;          // staged input rows per plane
 constexpr int TC_NFRAG = 15;                       // weight fragments: kd x kh-pair
-constexpr int TC_PP = 11;                          // floats per voxel in the P row (10 used + 1: odd pitch, conflict-free reads)
 
 struct ThinParams {
   const void* x;       // bf16 [N][D][H][W][ldx]
@@ -49,7 +45,7 @@ __global__ void thin_pack_fwd_kernel(const float* __restrict__ w, __bf16* __rest
   const int kd = f / 3, khp = f % 3, n = l & 15, kb = l >> 4;
   const int kh = 2 * khp + (kb >> 1), ci = (kb & 1) * 8 + j, kw = n >> 1, co = n & 1;
   float v = 0.f;
-  if (kh < TC_K && n < 2 * TC_K) v = w[(((co * TC_CIN + ci) * TC_K + kd) * TC_K + kh) * TC_K + kw];
+  if (kh < T5_K && n < 2 * T5_K) v = w[(((co * T5_CIN + ci) * T5_K + kd) * T5_K + kh) * T5_K + kw];
   out[i] = (__bf16)v;
 }
 
@@ -58,10 +54,10 @@ template <int NTW>
 __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W = NTW * 32;
-  constexpr int plane_bytes = TC_ROWS * W * 32;
-  constexpr int PROW = (W + 4) * TC_PP;                             // floats per P row
-  unsigned char* xs = smem;                                         // [2][TC_ROWS][W][16] bf16
-  float* prow = reinterpret_cast<float*>(smem + 2 * plane_bytes);   // [2][4 rows][W + 4][TC_PP]
+  constexpr int plane_bytes = T5_ROWS * W * 32;
+  constexpr int PROW = (W + 4) * T5_PP;                             // floats per P row
+  unsigned char* xs = smem;                                         // [2][T5_ROWS][W][16] bf16
+  float* prow = reinterpret_cast<float*>(smem + 2 * plane_bytes);   // [2][4 rows][W + 4][T5_PP]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = wave & 3, hf = wave >> 2;
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
   const int seg = b % p.nseg; b /= p.nseg;
   const int strip = b % p.nstrip;
   const int n_img = b / p.nstrip;
-  const int h0 = strip * TC_BH;
+  const int h0 = strip * T5_BH;
   const int d0 = seg * p.dseg, d1 = min(p.D, d0 + p.dseg);
 
   // weights: 15 fragments in registers for the whole kernel
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
 #pragma unroll
   for (int f = 0; f < TC_NFRAG; ++f) wf[f] = __builtin_bit_cast(bf16x8, p.wfrag[f * 64 + lane]);
 
-  // staging: 16-byte pieces of the plane, piece = (row, w, half); pieces per thread = TC_ROWS * W * 2 / 512 = NTW
+  // staging: 16-byte pieces of the plane, piece = (row, w, half); pieces per thread = T5_ROWS * W * 2 / 512 = NTW
   const uint32_t img_bytes = (uint32_t)p.D * p.H * p.W * p.ldx * 2u;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(p.x)) + (int64_t)n_img * img_bytes, 0, img_bytes,
@@ -117,8 +113,8 @@ __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       float* q = prow + (c * 4 + r) * PROW;
-      if (lane < 2 * TC_PP) q[lane] = 0.f;
-      if (lane < 2 * TC_PP) q[(W + 2) * TC_PP + lane] = 0.f;
+      if (lane < 2 * T5_PP) q[lane] = 0.f;
+      if (lane < 2 * T5_PP) q[(W + 2) * T5_PP + lane] = 0.f;
     }
   }
   const float bias_v = p.bias ? p.bias[lane & 1] : 0.f;
@@ -168,11 +164,11 @@ __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
     const int dout = dp - 2;
     const bool live = (dout >= d0) & (dout < d1) & (oh < p.H);
     float* pw_ = prow + ((buf * 4) + r) * PROW;   // the P copy alternates with the plane buffer
-    if (live && m < 2 * TC_K) {
+    if (live && m < 2 * T5_K) {
 #pragma unroll
       for (int t = 0; t < NTW; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pw_[(2 + hf * (W / 2) + t * 16 + kb * 4 + i) * TC_PP + m] = acc[SD][t][i];
+        for (int i = 0; i < 4; ++i) pw_[(2 + hf * (W / 2) + t * 16 + kb * 4 + i) * T5_PP + m] = acc[SD][t][i];
     }
 #pragma unroll
     for (int t = 0; t < NTW; ++t) acc[SD][t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -188,7 +184,7 @@ __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
         if (wl < W / 2) {
           float s = bias_v;
 #pragma unroll
-          for (int kw = 0; kw < TC_K; ++kw) s += pw_[(w + kw) * TC_PP + kw * 2 + co];
+          for (int kw = 0; kw < T5_K; ++kw) s += pw_[(w + kw) * T5_PP + kw * 2 + co];
           yrow[(int64_t)w * p.ldy + co] = s;
         }
       }
@@ -206,16 +202,6 @@ __global__ __launch_bounds__(512) void thin_fwd_kernel(const ThinParams p) {
   }
 }
 
-size_t thin_fwd_smem(int W) { return (size_t)2 * TC_ROWS * W * 32 + (size_t)2 * TC_BH * (W + 4) * TC_PP * 4; }
-
-bool thin_shape_ok(const rehr_direct_conv_desc& d) {
-  return d.Cin == TC_CIN && d.Cout == 2 && d.KD == TC_K && d.KH == TC_K && d.KW == TC_K && d.sd == 1 && d.sh == 1 &&
-         d.sw == 1 && d.pd == 2 && d.ph == 2 && d.pw == 2 && d.Do == d.Di && d.Ho == d.Hi && d.Wo == d.Wi &&
-         d.Wi % 32 == 0 && d.Wi >= 32 && d.Wi <= 160 && d.ldx % 8 == 0 && d.ldx >= TC_CIN && d.ldy >= 2 &&
-         (int64_t)d.Di * d.Hi * d.Wi * d.ldx * 2 < ((int64_t)1 << 32);
-}
-
-
 // ------------------------------------------------------------------------------------------------------------------
 // Input gradient: dx[v][ci] = sum_{kd,kh,kw,co} dy[v + (kd-2, kh-2, kw-2)][co] * w[co][ci][4-kd][4-kh][4-kw]
 // GEMM with M = ci (weights, 13 fragments in registers), N = 16 voxels along w, K = (two (kd,kh) taps) x (8 kw slots,
@@ -224,8 +210,6 @@ bool thin_shape_ok(const rehr_direct_conv_desc& d) {
 // 4 output rows x W of a depth segment (wave = row x half row) and keeps a ring of six dY planes (8 rows each) in LDS.
 // The accumulator quad of a lane is 4 consecutive ci of one voxel: 8-byte bf16 stores, 512 contiguous bytes per wave.
 constexpr int TD_NFRAG = 13;           // 25 (kd,kh) taps in pairs
-constexpr int TD_RING = 6;
-constexpr int TD_PADW = 8;             // dY row: 2 zero voxels in front, 6 behind
 
 struct ThinDgradParams {
   const float* dy;     // fp32 [N][D][H][W][ldy]
@@ -245,9 +229,9 @@ __global__ void thin_pack_dgrad_kernel(const float* __restrict__ w, __bf16* __re
   const int ci = l & 15, kb = l >> 4;
   const int tap = 2 * j + (kb >> 1), kw = (kb & 1) * 4 + (e >> 1), co = e & 1;
   float v = 0.f;
-  if (tap < TC_K * TC_K && kw < TC_K) {
-    const int kd = tap / TC_K, kh = tap % TC_K;
-    v = w[(((co * TC_CIN + ci) * TC_K + (4 - kd)) * TC_K + (4 - kh)) * TC_K + (4 - kw)];
+  if (tap < T5_K * T5_K && kw < T5_K) {
+    const int kd = tap / T5_K, kh = tap % T5_K;
+    v = w[(((co * T5_CIN + ci) * T5_K + (4 - kd)) * T5_K + (4 - kh)) * T5_K + (4 - kw)];
   }
   out[i] = (__bf16)v;
 }
@@ -256,9 +240,9 @@ template <int NTW>
 __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W = NTW * 32;
-  constexpr int ROWB = (W + TD_PADW) * 4;          // bytes per dY row
-  constexpr int PLANEB = TC_ROWS * ROWB;
-  constexpr int NPIECE = (TC_ROWS * W + 511) / 512;  // voxels staged per thread and plane
+  constexpr int ROWB = (W + T5_PADW) * 4;          // bytes per dY row
+  constexpr int PLANEB = T5_ROWS * ROWB;
+  constexpr int NPIECE = (T5_ROWS * W + 511) / 512;  // voxels staged per thread and plane
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = wave & 3, hf = wave >> 2;
@@ -266,7 +250,7 @@ __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p
   const int seg = b % p.nseg; b /= p.nseg;
   const int strip = b % p.nstrip;
   const int n_img = b / p.nstrip;
-  const int h0 = strip * TC_BH;
+  const int h0 = strip * T5_BH;
   const int d0 = seg * p.dseg, d1 = min(p.D, d0 + p.dseg);
 
   bf16x8 wf[TD_NFRAG];
@@ -274,8 +258,8 @@ __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p
   for (int f = 0; f < TD_NFRAG; ++f) wf[f] = __builtin_bit_cast(bf16x8, p.wfrag[f * 64 + lane]);
 
   // zero the row pads of every ring slot once (staging only ever writes voxels 0 .. W-1)
-  for (int i = tid; i < TD_RING * TC_ROWS * TD_PADW; i += 512) {
-    const int pv = i % TD_PADW, row = i / TD_PADW;
+  for (int i = tid; i < T5_RING * T5_ROWS * T5_PADW; i += 512) {
+    const int pv = i % T5_PADW, row = i / T5_PADW;
     const int vox = pv < 2 ? pv : W + pv;
     *reinterpret_cast<uint32_t*>(smem + row * ROWB + vox * 4) = 0u;
   }
@@ -288,9 +272,9 @@ __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p
     const int piece = tid + 512 * i;
     const int w = piece % W, row = piece / W;
     const int ih = h0 - 2 + row;
-    const bool ok = (piece < TC_ROWS * W) & ((unsigned)ih < (unsigned)p.H);
+    const bool ok = (piece < T5_ROWS * W) & ((unsigned)ih < (unsigned)p.H);
     pvox[i] = ok ? ih * p.W + w : -1;
-    plds[i] = (piece < TC_ROWS * W) ? row * ROWB + (w + 2) * 4 : -1;
+    plds[i] = (piece < T5_ROWS * W) ? row * ROWB + (w + 2) * 4 : -1;
   }
   float2 rx[NPIECE];
   auto fetch = [&](int dp) {
@@ -337,9 +321,9 @@ __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p
     int off[TD_NFRAG];
 #pragma unroll
     for (int j = 0; j < TD_NFRAG; ++j) {
-      const int t0 = 2 * j, t1 = (2 * j + 1 < TC_K * TC_K) ? 2 * j + 1 : 2 * j;   // the 26th tap has zero weights
-      const int o0 = ((P + t0 / TC_K) % TD_RING) * PLANEB + (t0 % TC_K) * ROWB;
-      const int o1 = ((P + t1 / TC_K) % TD_RING) * PLANEB + (t1 % TC_K) * ROWB;
+      const int t0 = 2 * j, t1 = (2 * j + 1 < T5_K * T5_K) ? 2 * j + 1 : 2 * j;   // the 26th tap has zero weights
+      const int o0 = ((P + t0 / T5_K) % T5_RING) * PLANEB + (t0 % T5_K) * ROWB;
+      const int o1 = ((P + t1 / T5_K) % T5_RING) * PLANEB + (t1 % T5_K) * ROWB;
       off[j] = (hi ? o1 : o0) + r * ROWB + lbase;
     }
     f32x4 acc[NTW];
@@ -362,7 +346,7 @@ __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p
         *reinterpret_cast<bf16x4*>(row + (int64_t)t * 16 * p.lddx) = o;
       }
     }
-    stage((P + 5) % TD_RING);   // plane d + 3 takes the slot plane d - 3 left
+    stage((P + 5) % T5_RING);   // plane d + 3 takes the slot plane d - 3 left
     __syncthreads();
   };
 
@@ -385,16 +369,13 @@ __global__ __launch_bounds__(512) void thin_dgrad_kernel(const ThinDgradParams p
 // A block owns 4 x rows of a depth segment and marches over the x planes (wave = 32-voxel chunk of the row, all 25
 // accumulator tiles = 100 registers); per x row a wave reads 5 shifted A fragments and, for each of the five dY planes
 // in the ring, one B fragment: 25 MFMAs per 10 fragment reads.  Partial sums go to one slab per block, summed in a
-// fixed order by thin_wgrad_reduce_kernel (bitwise reproducible), which also writes the torch weight layout.
-constexpr int TW_ROWS = TC_BH + 4;     // dY rows per plane
-constexpr int TW_SLAB = 25 * 16 * 16;  // floats per block: [kd*5 + kw][ci][n = kh*2 + co]
-constexpr int TW_SLABF = TW_SLAB + 16; // + the block's column sums of dY (bias gradient) in the first two extra slots
+// fixed order by thin5_wgrad_reduce (bitwise reproducible), which also writes the torch weight layout.
 
 struct ThinWgradParams {
   const void* x;       // bf16 [N][D][H][W][ldx]
   const float* dy;     // fp32 [N][D][H][W][ldy]
   int ldx, ldy, N, D, H, W;
-  float* slabs;        // [blocks][TW_SLAB]
+  float* slabs;        // [blocks][T5_SLAB]
   int dseg, nseg, nstrip;
 };
 
@@ -403,9 +384,9 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W = NW * 32, NTHR = 64 * NW;
   constexpr int XROWB = (W + 4) * 32;                 // x row: 2 zero voxels either side
-  constexpr int XBUF = TC_BH * XROWB;
+  constexpr int XBUF = T5_BH * XROWB;
   constexpr int DROWB = W * 2 + 16;                   // one (row, co) line of dY, bf16
-  constexpr int DPLANE = TW_ROWS * 2 * DROWB;
+  constexpr int DPLANE = T5_ROWS * 2 * DROWB;
   unsigned char* xs = smem;                           // [2][4 rows][W + 4][16]
   unsigned char* ds = smem + 2 * XBUF;                // [6][8 rows][2 co][W (+8)]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -414,11 +395,11 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
   const int seg = b % p.nseg; b /= p.nseg;
   const int strip = b % p.nstrip;
   const int n_img = b / p.nstrip;
-  const int h0 = strip * TC_BH;
+  const int h0 = strip * T5_BH;
   const int d0 = seg * p.dseg, d1 = min(p.D, d0 + p.dseg);
 
   // zero pads of the x rows (both buffers), once
-  for (int i = tid; i < 2 * TC_BH * 4 * 2; i += NTHR) {
+  for (int i = tid; i < 2 * T5_BH * 4 * 2; i += NTHR) {
     const int half = i & 1, pv = (i >> 1) & 3, row = i >> 3;
     const int vox = pv < 2 ? pv : W + pv;
     *reinterpret_cast<u32x4*>(xs + row * XROWB + vox * 32 + half * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -463,7 +444,7 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
     const int ih = h0 - 2 + row;
     yvox[i] = ((unsigned)ih < (unsigned)p.H) ? ih * p.W + w : -1;
     ylds[i] = row * 2 * DROWB + w * 2;
-    yown[i] = (row >= 2) & (row < 2 + TC_BH);
+    yown[i] = (row >= 2) & (row < 2 + T5_BH);
   }
   float ry[2][4];
   float db0 = 0.f, db1 = 0.f;
@@ -496,7 +477,7 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
   const int abase = (32 * c + 8 * grp + qq) * 32 + pp * 8;   // + row * XROWB + kw * 32 (the +2 pad and the -2 shift cancel)
   // B (dY): lane (n = kh*2 + co, kb): row (r + 4 - kh), line co, voxels 32c + 8kb .. +7
   const int nn = lane & 15, kb = lane >> 4;
-  const int khl = (nn >> 1) < TC_K ? (nn >> 1) : TC_K - 1, col = nn & 1;
+  const int khl = (nn >> 1) < T5_K ? (nn >> 1) : T5_K - 1, col = nn & 1;
   const int bbase = ((4 - khl) * 2 + col) * DROWB + (32 * c + 8 * kb) * 2;   // + r * 2 * DROWB
 
   f32x4 acc[25];
@@ -528,22 +509,22 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
     fetch_y(dx + 3);
     const unsigned char* xb = xs + buf * XBUF;
 #pragma unroll
-    for (int r = 0; r < TC_BH; ++r) {
-      bf16x8 a[TC_K];
+    for (int r = 0; r < T5_BH; ++r) {
+      bf16x8 a[T5_K];
 #pragma unroll
-      for (int kw = 0; kw < TC_K; ++kw) a[kw] = frag_a(xb + r * XROWB + kw * 32 + abase);
+      for (int kw = 0; kw < T5_K; ++kw) a[kw] = frag_a(xb + r * XROWB + kw * 32 + abase);
 #pragma unroll
-      for (int kd = 0; kd < TC_K; ++kd) {
-        const int slot = (P + 4 - kd) % TD_RING;
+      for (int kd = 0; kd < T5_K; ++kd) {
+        const int slot = (P + 4 - kd) % T5_RING;
         const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(ds + slot * DPLANE + r * 2 * DROWB + bbase);
 #pragma unroll
-        for (int kw = 0; kw < TC_K; ++kw)
+        for (int kw = 0; kw < T5_K; ++kw)
           acc[kd * 5 + kw] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[kw], bfr, acc[kd * 5 + kw], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);   // one x row per scheduling region: bounds the fragment registers in flight
     }
     stage_x(buf ^ 1);
-    stage_y((P + 5) % TD_RING);
+    stage_y((P + 5) % T5_RING);
     __syncthreads();
     buf ^= 1;
   };
@@ -560,8 +541,8 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
   // block sum over the waves (LDS), then the slab; accumulator register i of lane (n = l & 15, q = l >> 4) is
   // C[m = ci = 4q + i][n]
   __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);       // [NW][TW_SLAB] would not fit: reduce tile by tile
-  float* slab = p.slabs + (int64_t)blockIdx.x * TW_SLABF;
+  float* red = reinterpret_cast<float*>(smem);       // [NW][T5_SLAB] would not fit: reduce tile by tile
+  float* slab = p.slabs + (int64_t)blockIdx.x * T5_SLABF;
   {  // bias gradient: wave sums, then the block
     db0 = wave_sum(db0);
     db1 = wave_sum(db1);
@@ -571,7 +552,7 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
       float sdb = 0.f;
 #pragma unroll
       for (int w2 = 0; w2 < NW; ++w2) sdb += red[w2 * 2 + tid];
-      slab[TW_SLAB + tid] = sdb;
+      slab[T5_SLAB + tid] = sdb;
     }
     __syncthreads();
   }
@@ -590,89 +571,22 @@ __global__ __launch_bounds__(64 * NW) void thin_wgrad_kernel(const ThinWgradPara
   }
 }
 
-// dw (2,16,5,5,5) = sum over block slabs, fixed order; slab index [(kd*5 + kw)][ci][kh*2 + co]
-// 8 threads share an output element (thread (e, g) sums the blocks g, g + 8, ...; fixed-order combine through LDS): one
-// thread per element walking every block's slab was a 0.29 ms latency chain at 160^3
-__global__ __launch_bounds__(256) void thin_wgrad_reduce_kernel(const float* __restrict__ slabs, int nblocks, float* __restrict__ dw,
-                                                             float* __restrict__ dbias) {
-  constexpr int G = 8, EPB = 256 / G, NDW = 2 * TC_CIN * 125;
-  __shared__ float part[256];
-  const int el = threadIdx.x % EPB, g = threadIdx.x / EPB;
-  const int i = blockIdx.x * EPB + el;   // index into dw (2,16,5,5,5), then the two bias gradients
-  int si = -1;
-  if (i < NDW) {
-    const int kw = i % 5, kh = (i / 5) % 5, kd = (i / 25) % 5, ci = (i / 125) % TC_CIN, co = i / (125 * TC_CIN);
-    si = ((kd * 5 + kw) * 16 + ci) * 16 + kh * 2 + co;
-  } else if (i < NDW + 2) {
-    si = TW_SLAB + (i - NDW);
-  }
-  float s0 = 0.f, s1 = 0.f;
-  if (si >= 0) {
-    int bq = g;
-    for (; bq + G < nblocks; bq += 2 * G) {
-      s0 += slabs[(int64_t)bq * TW_SLABF + si];
-      s1 += slabs[(int64_t)(bq + G) * TW_SLABF + si];
-    }
-    for (; bq < nblocks; bq += G) s0 += slabs[(int64_t)bq * TW_SLABF + si];
-  }
-  part[threadIdx.x] = s0 + s1;
-  __syncthreads();
-  if (g == 0 && si >= 0) {
-    float s = part[el];
-#pragma unroll
-    for (int q = 1; q < G; ++q) s += part[q * EPB + el];
-    if (i < NDW) dw[i] = s;
-    else if (dbias != nullptr) dbias[i - NDW] = s;
-  }
-}
-
 }  // namespace
 
-static void thin_segments(const rehr_direct_conv_desc& d, int& nstrip, int& dseg, int& nseg) {
-  nstrip = (d.Hi + TC_BH - 1) / TC_BH;
-  // depth segments: enough blocks for the chip, each long enough to amortise the halo planes
-  int ns = 1;
-  while ((int64_t)d.N * nstrip * ns < 512 && d.Di / (ns * 2) >= 16) ns *= 2;
-  dseg = (d.Di + ns - 1) / ns;
-  nseg = (d.Di + dseg - 1) / dseg;
-}
+constexpr Thin5Prec BF16 = {2, 8, 160, (int64_t)TC_NFRAG * 64 * 16};
 
 extern "C" int64_t rehr_conv5_thin_workspace_bytes(const rehr_direct_conv_desc* dp) {
-  if (dp == nullptr) return REHR_EINVAL;
-  if (!thin_shape_ok(*dp)) return REHR_ENOSUP;
-  int nstrip, dseg, nseg;
-  thin_segments(*dp, nstrip, dseg, nseg);
-  const int64_t slabs = (int64_t)dp->N * nstrip * nseg * TW_SLABF * 4;
-  const int64_t pack = (int64_t)TC_NFRAG * 64 * 16;
-  return slabs > pack ? slabs : pack;
+  return dp == nullptr ? REHR_EINVAL : thin5_workspace_bytes(*dp, BF16);
 }
 
-extern "C" int rehr_conv5_thin_supported(const rehr_direct_conv_desc* d) { return d != nullptr && thin_shape_ok(*d) ? 1 : 0; }
-
-#define TC_SWITCH(KERNEL, THREADS_OF)                                                                               \
-  switch (d.Wi / 32) {                                                                                              \
-    case 1: TC_LAUNCH(KERNEL, 1, THREADS_OF(1)); break;                                                             \
-    case 2: TC_LAUNCH(KERNEL, 2, THREADS_OF(2)); break;                                                             \
-    case 3: TC_LAUNCH(KERNEL, 3, THREADS_OF(3)); break;                                                             \
-    case 4: TC_LAUNCH(KERNEL, 4, THREADS_OF(4)); break;                                                             \
-    case 5: TC_LAUNCH(KERNEL, 5, THREADS_OF(5)); break;                                                             \
-    default: return REHR_ENOSUP;                                                                                    \
-  }
-#define TC_LAUNCH(KERNEL, NT_, THREADS)                                                                             \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL<NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)smem);                                                                           \
-    hipLaunchKernelGGL(KERNEL<NT_>, dim3((unsigned)blocks), dim3(THREADS), smem, st, p);                            \
-  } while (0)
-#define TC_T512(n) 512
-#define TC_T64N(n) (64 * (n))
+extern "C" int rehr_conv5_thin_supported(const rehr_direct_conv_desc* d) { return d != nullptr && thin5_shape_ok(*d, BF16) ? 1 : 0; }
 
 extern "C" int rehr_conv5_thin_fwd_bf16(const rehr_direct_conv_desc* dp, void* workspace, int64_t workspace_bytes,
                                         void* stream) {
-  if (dp == nullptr || dp->x == nullptr || dp->w == nullptr || dp->y == nullptr || workspace == nullptr) return REHR_EINVAL;
+  if (dp == nullptr || dp->x == nullptr || dp->w == nullptr || dp->y == nullptr) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
-  if (!thin_shape_ok(d)) return REHR_ENOSUP;
-  if (workspace_bytes < rehr_conv5_thin_workspace_bytes(dp) || d.act != REHR_ACT_NONE || d.stats_mode != 0) return REHR_EINVAL;
+  if (const int rc = thin5_admit(d, workspace, workspace_bytes, BF16)) return rc;
+  if (d.act != REHR_ACT_NONE || d.stats_mode != 0) return REHR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(thin_pack_fwd_kernel, dim3((TC_NFRAG * 512 + 255) / 256), dim3(256), 0, st, d.w,
                      reinterpret_cast<__bf16*>(workspace));
@@ -680,20 +594,19 @@ extern "C" int rehr_conv5_thin_fwd_bf16(const rehr_direct_conv_desc* dp, void* w
   p.x = d.x; p.ldx = d.ldx; p.N = d.N; p.D = d.Di; p.H = d.Hi; p.W = d.Wi;
   p.wfrag = reinterpret_cast<const u32x4*>(workspace);
   p.bias = d.bias; p.y = d.y; p.ldy = d.ldy;
-  thin_segments(d, p.nstrip, p.dseg, p.nseg);
-  const int64_t blocks = (int64_t)d.N * p.nstrip * p.nseg;
-  const size_t smem = thin_fwd_smem(d.Wi);
-  TC_SWITCH(thin_fwd_kernel, TC_T512)
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  const int64_t blocks = thin5_segments(d, p.nstrip, p.dseg, p.nseg);
+  const size_t smem = (size_t)2 * T5_ROWS * d.Wi * 32 + (size_t)2 * T5_BH * (d.Wi + 4) * T5_PP * 4;
+  return thin5_for_width<5>(d.Wi / 32, [&](auto n) {
+    return thin5_launch(thin_fwd_kernel<decltype(n)::value>, blocks, 512, smem, st, p);
+  });
 }
 
 extern "C" int rehr_conv5_thin_dgrad_bf16(const rehr_direct_conv_desc* dp, void* dx, int32_t lddx, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (dp == nullptr || dp->w == nullptr || dp->y == nullptr || dx == nullptr || workspace == nullptr) return REHR_EINVAL;
+  if (dp == nullptr || dp->w == nullptr || dp->y == nullptr || dx == nullptr) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
-  if (!thin_shape_ok(d)) return REHR_ENOSUP;
-  if (workspace_bytes < rehr_conv5_thin_workspace_bytes(dp) || lddx < TC_CIN || lddx % 4) return REHR_EINVAL;
+  if (const int rc = thin5_admit(d, workspace, workspace_bytes, BF16)) return rc;
+  if (lddx < T5_CIN || lddx % 4) return REHR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(thin_pack_dgrad_kernel, dim3((TD_NFRAG * 512 + 255) / 256), dim3(256), 0, st, d.w,
                      reinterpret_cast<__bf16*>(workspace));
@@ -701,31 +614,26 @@ extern "C" int rehr_conv5_thin_dgrad_bf16(const rehr_direct_conv_desc* dp, void*
   p.dy = d.y; p.ldy = d.ldy; p.N = d.N; p.D = d.Di; p.H = d.Hi; p.W = d.Wi;
   p.wfrag = reinterpret_cast<const u32x4*>(workspace);
   p.dx = dx; p.lddx = lddx;
-  thin_segments(d, p.nstrip, p.dseg, p.nseg);
-  const int64_t blocks = (int64_t)d.N * p.nstrip * p.nseg;
-  const size_t smem = (size_t)TD_RING * TC_ROWS * (d.Wi + TD_PADW) * 4;
-  TC_SWITCH(thin_dgrad_kernel, TC_T512)
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  const int64_t blocks = thin5_segments(d, p.nstrip, p.dseg, p.nseg);
+  const size_t smem = (size_t)T5_RING * T5_ROWS * (d.Wi + T5_PADW) * 4;
+  return thin5_for_width<5>(d.Wi / 32, [&](auto n) {
+    return thin5_launch(thin_dgrad_kernel<decltype(n)::value>, blocks, 512, smem, st, p);
+  });
 }
 
 extern "C" int rehr_conv5_thin_wgrad_bf16(const rehr_direct_conv_desc* dp, float* dw, float* dbias, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (dp == nullptr || dp->x == nullptr || dp->y == nullptr || dw == nullptr || workspace == nullptr) return REHR_EINVAL;
+  if (dp == nullptr || dp->x == nullptr || dp->y == nullptr || dw == nullptr) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
-  if (!thin_shape_ok(d)) return REHR_ENOSUP;
-  if (workspace_bytes < rehr_conv5_thin_workspace_bytes(dp)) return REHR_EINVAL;
+  if (const int rc = thin5_admit(d, workspace, workspace_bytes, BF16)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ThinWgradParams p;
   p.x = d.x; p.dy = d.y; p.ldx = d.ldx; p.ldy = d.ldy; p.N = d.N; p.D = d.Di; p.H = d.Hi; p.W = d.Wi;
   p.slabs = reinterpret_cast<float*>(workspace);
-  thin_segments(d, p.nstrip, p.dseg, p.nseg);
-  const int64_t blocks = (int64_t)d.N * p.nstrip * p.nseg;
-  const size_t smem = (size_t)2 * TC_BH * (d.Wi + 4) * 32 + (size_t)TD_RING * TW_ROWS * 2 * (d.Wi * 2 + 16);
-  TC_SWITCH(thin_wgrad_kernel, TC_T64N)
-  REHR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(thin_wgrad_reduce_kernel, dim3((2 * TC_CIN * 125 + 2 + 31) / 32), dim3(256), 0, st, p.slabs,
-                     (int)blocks, dw, dbias);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  const int64_t blocks = thin5_segments(d, p.nstrip, p.dseg, p.nseg);
+  const size_t smem = (size_t)2 * T5_BH * (d.Wi + 4) * 32 + (size_t)T5_RING * T5_ROWS * 2 * (d.Wi * 2 + 16);
+  const int rc = thin5_for_width<5>(d.Wi / 32, [&](auto n) {   // a wave per 32 voxels of the row
+    return thin5_launch(thin_wgrad_kernel<decltype(n)::value>, blocks, 64 * decltype(n)::value, smem, st, p);
+  });
+  return rc != REHR_OK ? rc : thin5_wgrad_reduce(p.slabs, (int)blocks, dw, dbias, st);
 }

@@ -14,22 +14,14 @@
 // On the VALU kernels of direct_conv.hip the layer costs 7.0 ms of a 52.6 ms cfg-3 step (profiles/r02_seg_kernel_stats.csv:
 // 2.33 + 1.94 + 2.77 ms); the fp32 matrix pipe has the vector pipe's peak, the gain comes from the 5-fold fragment reuse
 // and from weights that never leave the registers.
-#include "common.h"
-#include <type_traits>
+#include "direct_shared.h"
 
 namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int TF_CIN = 16, TF_K = 5, TF_BH = 4;
-constexpr int TF_ROWS = TF_BH + TF_K - 1;
-constexpr int TF_PP = 11;               // floats per voxel in the P row (10 used, odd pitch)
 constexpr int TF_NW_FWD = 100;          // weight fragments of the forward: [kd][kh][channel quad]
 constexpr int TF_NW_DG = 75;            // input gradient: [tap (kd,kh)][kw pair]
-constexpr int TF_RING = 6;
-constexpr int TF_PADW = 8;              // dY row of the input gradient: 2 zero voxels in front, 6 behind
-constexpr int TF_SLAB = 25 * 16 * 16;   // weight-gradient partial sums per block: [kd*5 + kw][ci][kh*2 + co]
-constexpr int TF_SLABF = TF_SLAB + 16;  // + column sums of dY
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
@@ -49,19 +41,19 @@ __global__ void thinf_pack_fwd_kernel(const float* __restrict__ w, float* __rest
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= TF_NW_FWD * 64) return;
   const int l = i & 63, f = i >> 6;
-  const int cq = f & 3, kh = (f >> 2) % TF_K, kd = (f >> 2) / TF_K;
+  const int cq = f & 3, kh = (f >> 2) % T5_K, kd = (f >> 2) / T5_K;
   const int n = l & 15, kq = l >> 4, kw = n >> 1, co = n & 1;
-  out[i] = (n < 2 * TF_K) ? w[(((co * TF_CIN + 4 * cq + kq) * TF_K + kd) * TF_K + kh) * TF_K + kw] : 0.f;
+  out[i] = (n < 2 * T5_K) ? w[(((co * T5_CIN + 4 * cq + kq) * T5_K + kd) * T5_K + kh) * T5_K + kw] : 0.f;
 }
 
 template <int NTW>
 __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W = NTW * 32;
-  constexpr int plane_bytes = TF_ROWS * W * 32;                     // 8 channels x 4 B per voxel
-  constexpr int PROW = (W + 4) * TF_PP;
-  unsigned char* xs = smem;                                         // [2][TF_ROWS][W][8] fp32
-  float* prow = reinterpret_cast<float*>(smem + 2 * plane_bytes);   // [2][4 rows][W + 4][TF_PP]
+  constexpr int plane_bytes = T5_ROWS * W * 32;                     // 8 channels x 4 B per voxel
+  constexpr int PROW = (W + 4) * T5_PP;
+  unsigned char* xs = smem;                                         // [2][T5_ROWS][W][8] fp32
+  float* prow = reinterpret_cast<float*>(smem + 2 * plane_bytes);   // [2][4 rows][W + 4][T5_PP]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = wave & 3, hf = wave >> 2;
@@ -69,7 +61,7 @@ __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
   const int seg = b % p.nseg; b /= p.nseg;
   const int strip = b % p.nstrip;
   const int n_img = b / p.nstrip;
-  const int h0 = strip * TF_BH;
+  const int h0 = strip * T5_BH;
   const int d0 = seg * p.dseg, d1 = min(p.D, d0 + p.dseg);
 
   // staging: 16-byte pieces of (plane, channel half): piece = (row, w, quad); NTW pieces per thread
@@ -104,8 +96,8 @@ __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       float* q = prow + (c * 4 + r) * PROW;
-      if (lane < 2 * TF_PP) q[lane] = 0.f;
-      if (lane < 2 * TF_PP) q[(W + 2) * TF_PP + lane] = 0.f;
+      if (lane < 2 * T5_PP) q[lane] = 0.f;
+      if (lane < 2 * T5_PP) q[(W + 2) * T5_PP + lane] = 0.f;
     }
   }
   const float bias_v = p.bias ? p.bias[lane & 1] : 0.f;
@@ -130,12 +122,12 @@ __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
     const unsigned char* xb = xs + buf * plane_bytes;
     // group g = (kh, channel quad of this half): 5 weight fragments (kd, from L1 two groups ahead) and one A dword per
     // tile (from LDS one group ahead); 5 * NTW MFMAs per group
-    float bw[3][TF_K], a[2][NTW];
-    auto ldw = [&](float (&dst)[TF_K], const int g_) {
+    float bw[3][T5_K], a[2][NTW];
+    auto ldw = [&](float (&dst)[T5_K], const int g_) {
 #pragma unroll
-      for (int kd = 0; kd < TF_K; ++kd)
+      for (int kd = 0; kd < T5_K; ++kd)
         dst[kd] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                      rsw, wlane, ((kd * TF_K + (g_ >> 1)) * 4 + hc * 2 + (g_ & 1)) * 256, 0));
+                      rsw, wlane, ((kd * T5_K + (g_ >> 1)) * 4 + hc * 2 + (g_ & 1)) * 256, 0));
     };
     auto lda = [&](float (&dst)[NTW], const int g_) {
 #pragma unroll
@@ -146,14 +138,14 @@ __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
     ldw(bw[1], 1);
     lda(a[0], 0);
 #pragma unroll
-    for (int g = 0; g < 2 * TF_K; ++g) {
-      if (g + 2 < 2 * TF_K) ldw(bw[(g + 2) % 3], g + 2);
-      if (g + 1 < 2 * TF_K) lda(a[(g + 1) & 1], g + 1);
+    for (int g = 0; g < 2 * T5_K; ++g) {
+      if (g + 2 < 2 * T5_K) ldw(bw[(g + 2) % 3], g + 2);
+      if (g + 1 < 2 * T5_K) lda(a[(g + 1) & 1], g + 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int t = 0; t < NTW; ++t)
 #pragma unroll
-        for (int kd = 0; kd < TF_K; ++kd) {
+        for (int kd = 0; kd < T5_K; ++kd) {
           const int s = (S0 - kd + 5) % 5;   // output plane dp - kd + 2
           acc[s][t] = mfma4(a[g & 1][t], bw[g % 3][kd], acc[s][t]);
         }
@@ -175,11 +167,11 @@ __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
     const int dout = dp - 2;
     const bool live = (dout >= d0) & (dout < d1) & (oh < p.H);
     float* pw_ = prow + ((pbuf * 4) + r) * PROW;
-    if (live && m < 2 * TF_K) {
+    if (live && m < 2 * T5_K) {
 #pragma unroll
       for (int t = 0; t < NTW; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pw_[(2 + hf * (W / 2) + t * 16 + kq * 4 + i) * TF_PP + m] = acc[SD][t][i];
+        for (int i = 0; i < 4; ++i) pw_[(2 + hf * (W / 2) + t * 16 + kq * 4 + i) * T5_PP + m] = acc[SD][t][i];
     }
 #pragma unroll
     for (int t = 0; t < NTW; ++t) acc[SD][t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(512) void thinf_fwd_kernel(const ThinF32Params p) {
         if (wl < W / 2) {
           float s = bias_v;
 #pragma unroll
-          for (int kw = 0; kw < TF_K; ++kw) s += pw_[(w + kw) * TF_PP + kw * 2 + co];
+          for (int kw = 0; kw < T5_K; ++kw) s += pw_[(w + kw) * T5_PP + kw * 2 + co];
           yrow[(int64_t)w * p.ldy + co] = s;
         }
       }
@@ -229,18 +221,18 @@ __global__ void thinf_pack_dgrad_kernel(const float* __restrict__ w, float* __re
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= TF_NW_DG * 64) return;
   const int l = i & 63, f = i >> 6;
-  const int pr = f % 3, tap = f / 3, kd = tap / TF_K, kh = tap % TF_K;
+  const int pr = f % 3, tap = f / 3, kd = tap / T5_K, kh = tap % T5_K;
   const int ci = l & 15, kq = l >> 4, kw = 2 * pr + (kq >> 1), co = kq & 1;
-  out[i] = (kw < TF_K) ? w[(((co * TF_CIN + ci) * TF_K + (4 - kd)) * TF_K + (4 - kh)) * TF_K + (4 - kw)] : 0.f;
+  out[i] = (kw < T5_K) ? w[(((co * T5_CIN + ci) * T5_K + (4 - kd)) * T5_K + (4 - kh)) * T5_K + (4 - kw)] : 0.f;
 }
 
 template <int NTW>
 __global__ __launch_bounds__(512) void thinf_dgrad_kernel(const ThinF32DgradParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W = NTW * 32;
-  constexpr int ROWB = (W + TF_PADW) * 8;            // bytes per dY row (2 floats per voxel)
-  constexpr int PLANEB = TF_ROWS * ROWB;
-  constexpr int NPIECE = (TF_ROWS * W + 511) / 512;
+  constexpr int ROWB = (W + T5_PADW) * 8;            // bytes per dY row (2 floats per voxel)
+  constexpr int PLANEB = T5_ROWS * ROWB;
+  constexpr int NPIECE = (T5_ROWS * W + 511) / 512;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = wave & 3, hf = wave >> 2;
@@ -248,15 +240,15 @@ __global__ __launch_bounds__(512) void thinf_dgrad_kernel(const ThinF32DgradPara
   const int seg = b % p.nseg; b /= p.nseg;
   const int strip = b % p.nstrip;
   const int n_img = b / p.nstrip;
-  const int h0 = strip * TF_BH;
+  const int h0 = strip * T5_BH;
   const int d0 = seg * p.dseg, d1 = min(p.D, d0 + p.dseg);
 
   float wf[TF_NW_DG];
 #pragma unroll
   for (int f = 0; f < TF_NW_DG; ++f) wf[f] = p.wfrag[f * 64 + lane];
 
-  for (int i = tid; i < TF_RING * TF_ROWS * TF_PADW; i += 512) {   // row pads of every ring slot, once
-    const int pv = i % TF_PADW, row = i / TF_PADW;
+  for (int i = tid; i < T5_RING * T5_ROWS * T5_PADW; i += 512) {   // row pads of every ring slot, once
+    const int pv = i % T5_PADW, row = i / T5_PADW;
     const int vox = pv < 2 ? pv : W + pv;
     *reinterpret_cast<float2*>(smem + row * ROWB + vox * 8) = make_float2(0.f, 0.f);
   }
@@ -268,9 +260,9 @@ __global__ __launch_bounds__(512) void thinf_dgrad_kernel(const ThinF32DgradPara
     const int piece = tid + 512 * i;
     const int w = piece % W, row = piece / W;
     const int ih = h0 - 2 + row;
-    const bool ok = (piece < TF_ROWS * W) & ((unsigned)ih < (unsigned)p.H);
+    const bool ok = (piece < T5_ROWS * W) & ((unsigned)ih < (unsigned)p.H);
     pvox[i] = ok ? ih * p.W + w : -1;
-    plds[i] = (piece < TF_ROWS * W) ? row * ROWB + (w + 2) * 8 : -1;
+    plds[i] = (piece < T5_ROWS * W) ? row * ROWB + (w + 2) * 8 : -1;
   }
   float2 rx[NPIECE];
   auto fetch = [&](int dp) {
@@ -292,7 +284,7 @@ __global__ __launch_bounds__(512) void thinf_dgrad_kernel(const ThinF32DgradPara
 
   // B fragment of this lane: voxel hf*W/2 + 16 t + n + kw (stored index: + 2 pad - 2 shift), kw = 2 pr + (kq >> 1), channel kq & 1
   const int n = lane & 15, kq = lane >> 4;
-  const int lbase = (r * (W + TF_PADW) + hf * (W / 2) + n + (kq >> 1)) * 8 + (kq & 1) * 4;   // + kh * ROWB + pr * 16 + t * 128
+  const int lbase = (r * (W + T5_PADW) + hf * (W / 2) + n + (kq >> 1)) * 8 + (kq & 1) * 4;   // + kh * ROWB + pr * 16 + t * 128
 
   for (int s = 0; s < 5; ++s) {
     fetch(d0 - 2 + s);
@@ -312,8 +304,8 @@ __global__ __launch_bounds__(512) void thinf_dgrad_kernel(const ThinF32DgradPara
     for (int t = 0; t < NTW; ++t) {
       acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int tap = 0; tap < TF_K * TF_K; ++tap) {
-        const int off = ((P + tap / TF_K) % TF_RING) * PLANEB + (tap % TF_K) * ROWB;
+      for (int tap = 0; tap < T5_K * T5_K; ++tap) {
+        const int off = ((P + tap / T5_K) % T5_RING) * PLANEB + (tap % T5_K) * ROWB;
 #pragma unroll
         for (int pr = 0; pr < 3; ++pr) {
           const float bv = *reinterpret_cast<const float*>(smem + off + lbase + pr * 16 + t * 128);
@@ -326,7 +318,7 @@ __global__ __launch_bounds__(512) void thinf_dgrad_kernel(const ThinF32DgradPara
 #pragma unroll
       for (int t = 0; t < NTW; ++t) *reinterpret_cast<f32x4*>(row + (int64_t)t * 16 * p.lddx) = acc[t];
     }
-    stage((P + 5) % TF_RING);
+    stage((P + 5) % T5_RING);
     __syncthreads();
   };
 
@@ -345,7 +337,7 @@ struct ThinF32WgradParams {
   const float* x;      // [N][D][H][W][ldx]
   const float* dy;     // [N][D][H][W][ldy]
   int ldx, ldy, N, D, H, W;
-  float* slabs;        // [blocks][TF_SLABF]
+  float* slabs;        // [blocks][T5_SLABF]
   int dseg, nseg, nstrip;
 };
 
@@ -356,9 +348,9 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W = NW * 32, NTHR = 128 * NW;
   constexpr int XROWB = (W + 4) * 64;                 // x row: 16 channels x 4 B per voxel, 2 zero voxels either side
-  constexpr int XBUF = TF_BH * XROWB;
+  constexpr int XBUF = T5_BH * XROWB;
   constexpr int DROWB = W * 4 + 16;                   // one (row, co) line of dY
-  constexpr int DPLANE = TF_ROWS * 2 * DROWB;
+  constexpr int DPLANE = T5_ROWS * 2 * DROWB;
   unsigned char* xs = smem;                           // [2][4 rows][W + 4][16]
   unsigned char* ds = smem + 2 * XBUF;                // [6][8 rows][2 co][W (+4)]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -368,10 +360,10 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
   const int seg = b % p.nseg; b /= p.nseg;
   const int strip = b % p.nstrip;
   const int n_img = b / p.nstrip;
-  const int h0 = strip * TF_BH;
+  const int h0 = strip * T5_BH;
   const int d0 = seg * p.dseg, d1 = min(p.D, d0 + p.dseg);
 
-  for (int i = tid; i < 2 * TF_BH * 4 * 4; i += NTHR) {   // zero pads of the x rows (both buffers), once
+  for (int i = tid; i < 2 * T5_BH * 4 * 4; i += NTHR) {   // zero pads of the x rows (both buffers), once
     const int q4 = i & 3, pv = (i >> 2) & 3, row = i >> 4;
     const int vox = pv < 2 ? pv : W + pv;
     *reinterpret_cast<u32x4*>(xs + row * XROWB + vox * 64 + q4 * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -415,7 +407,7 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
     const int ih = h0 - 2 + row;
     yvox[i] = ((unsigned)ih < (unsigned)p.H) ? ih * p.W + w : -1;
     ylds[i] = row * 2 * DROWB + w * 4;
-    yown[i] = (row >= 2) & (row < 2 + TF_BH);
+    yown[i] = (row >= 2) & (row < 2 + T5_BH);
   }
   float2 ry[2];
   float db0 = 0.f, db1 = 0.f;
@@ -444,7 +436,7 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
   const int mm = lane & 15, kq = lane >> 4;
   const int abase = (32 * c + kq) * 64 + mm * 4;       // + row * XROWB + (4 j + kw) * 64
   // B: lane (n = kh*2 + co, kq) reads dy[row r + 4 - kh][co][32c + 4j + kq]
-  const int khl = (mm >> 1) < TF_K ? (mm >> 1) : TF_K - 1, col = mm & 1;
+  const int khl = (mm >> 1) < T5_K ? (mm >> 1) : T5_K - 1, col = mm & 1;
   const int bbase = ((4 - khl) * 2 + col) * DROWB + (32 * c + kq) * 4;   // + r * 2 * DROWB + j * 16
 
   f32x4 acc[25];
@@ -467,25 +459,25 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
     fetch_y(dx + 3);
     const unsigned char* xb = xs + buf * XBUF;
 #pragma unroll
-    for (int r2 = 0; r2 < TF_BH / 2; ++r2) {
-      const int r = rp * (TF_BH / 2) + r2;
+    for (int r2 = 0; r2 < T5_BH / 2; ++r2) {
+      const int r = rp * (T5_BH / 2) + r2;
 #pragma unroll 2
       for (int j = 0; j < 8; ++j) {
-        float a[TF_K];
+        float a[T5_K];
 #pragma unroll
-        for (int kw = 0; kw < TF_K; ++kw) a[kw] = *reinterpret_cast<const float*>(xb + r * XROWB + (4 * j + kw) * 64 + abase);
+        for (int kw = 0; kw < T5_K; ++kw) a[kw] = *reinterpret_cast<const float*>(xb + r * XROWB + (4 * j + kw) * 64 + abase);
 #pragma unroll
-        for (int kd = 0; kd < TF_K; ++kd) {
-          const int slot = (P + 4 - kd) % TF_RING;
+        for (int kd = 0; kd < T5_K; ++kd) {
+          const int slot = (P + 4 - kd) % T5_RING;
           const float bv = *reinterpret_cast<const float*>(ds + slot * DPLANE + r * 2 * DROWB + j * 16 + bbase);
 #pragma unroll
-          for (int kw = 0; kw < TF_K; ++kw) acc[kd * 5 + kw] = mfma4(a[kw], bv, acc[kd * 5 + kw]);
+          for (int kw = 0; kw < T5_K; ++kw) acc[kd * 5 + kw] = mfma4(a[kw], bv, acc[kd * 5 + kw]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     stage_x(buf ^ 1);
-    stage_y((P + 5) % TF_RING);
+    stage_y((P + 5) % T5_RING);
     __syncthreads();
     buf ^= 1;
   };
@@ -502,7 +494,7 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
   // block sum over the waves (LDS), then the slab; register i of lane (n = l & 15, q = l >> 4) is C[ci = 4q + i][n]
   __syncthreads();
   float* red = reinterpret_cast<float*>(smem);
-  float* slab = p.slabs + (int64_t)blockIdx.x * TF_SLABF;
+  float* slab = p.slabs + (int64_t)blockIdx.x * T5_SLABF;
   {
     db0 = wave_sum(db0);
     db1 = wave_sum(db1);
@@ -512,7 +504,7 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
       float sdb = 0.f;
 #pragma unroll
       for (int w2 = 0; w2 < 2 * NW; ++w2) sdb += red[w2 * 2 + tid];
-      slab[TF_SLAB + tid] = sdb;
+      slab[T5_SLAB + tid] = sdb;
     }
     __syncthreads();
   }
@@ -531,95 +523,24 @@ __global__ __launch_bounds__(128 * NW) void thinf_wgrad_kernel(const ThinF32Wgra
   }
 }
 
-// 8 threads share an output element (thread (e, g) sums the blocks g, g + 8, ...; fixed-order combine through LDS): one
-// thread per element walking every block's slab was a 0.29 ms latency chain at 160^3
-__global__ __launch_bounds__(256) void thinf_wgrad_reduce_kernel(const float* __restrict__ slabs, int nblocks, float* __restrict__ dw,
-                                                             float* __restrict__ dbias) {
-  constexpr int G = 8, EPB = 256 / G, NDW = 2 * TF_CIN * 125;
-  __shared__ float part[256];
-  const int el = threadIdx.x % EPB, g = threadIdx.x / EPB;
-  const int i = blockIdx.x * EPB + el;   // index into dw (2,16,5,5,5), then the two bias gradients
-  int si = -1;
-  if (i < NDW) {
-    const int kw = i % 5, kh = (i / 5) % 5, kd = (i / 25) % 5, ci = (i / 125) % TF_CIN, co = i / (125 * TF_CIN);
-    si = ((kd * 5 + kw) * 16 + ci) * 16 + kh * 2 + co;
-  } else if (i < NDW + 2) {
-    si = TF_SLAB + (i - NDW);
-  }
-  float s0 = 0.f, s1 = 0.f;
-  if (si >= 0) {
-    int bq = g;
-    for (; bq + G < nblocks; bq += 2 * G) {
-      s0 += slabs[(int64_t)bq * TF_SLABF + si];
-      s1 += slabs[(int64_t)(bq + G) * TF_SLABF + si];
-    }
-    for (; bq < nblocks; bq += G) s0 += slabs[(int64_t)bq * TF_SLABF + si];
-  }
-  part[threadIdx.x] = s0 + s1;
-  __syncthreads();
-  if (g == 0 && si >= 0) {
-    float s = part[el];
-#pragma unroll
-    for (int q = 1; q < G; ++q) s += part[q * EPB + el];
-    if (i < NDW) dw[i] = s;
-    else if (dbias != nullptr) dbias[i - NDW] = s;
-  }
-}
-
-bool thinf_shape_ok(const rehr_direct_conv_desc& d) {
-  return d.Cin == TF_CIN && d.Cout == 2 && d.KD == TF_K && d.KH == TF_K && d.KW == TF_K && d.sd == 1 && d.sh == 1 &&
-         d.sw == 1 && d.pd == 2 && d.ph == 2 && d.pw == 2 && d.Do == d.Di && d.Ho == d.Hi && d.Wo == d.Wi &&
-         d.Wi % 32 == 0 && d.Wi >= 32 && d.Wi <= 128 && d.ldx % 4 == 0 && d.ldx >= TF_CIN && d.ldy >= 2 &&
-         (int64_t)d.Di * d.Hi * d.Wi * d.ldx * 4 < ((int64_t)1 << 32);   // (W = 160 would spill in the forward kernel)
-}
-
-void thinf_segments(const rehr_direct_conv_desc& d, int& nstrip, int& dseg, int& nseg) {
-  nstrip = (d.Hi + TF_BH - 1) / TF_BH;
-  int ns = 1;
-  while ((int64_t)d.N * nstrip * ns < 512 && d.Di / (ns * 2) >= 16) ns *= 2;
-  dseg = (d.Di + ns - 1) / ns;
-  nseg = (d.Di + dseg - 1) / dseg;
-}
-
 }  // namespace
 
+constexpr Thin5Prec F32 = {4, 4, 128, (int64_t)TF_NW_FWD * 64 * 4};   // (W = 160 would spill in the forward kernel)
+
 extern "C" int64_t rehr_conv5_thin_f32_workspace_bytes(const rehr_direct_conv_desc* dp) {
-  if (dp == nullptr) return REHR_EINVAL;
-  if (!thinf_shape_ok(*dp)) return REHR_ENOSUP;
-  int nstrip, dseg, nseg;
-  thinf_segments(*dp, nstrip, dseg, nseg);
-  const int64_t slabs = (int64_t)dp->N * nstrip * nseg * TF_SLABF * 4;
-  const int64_t pack = (int64_t)TF_NW_FWD * 64 * 4;
-  return slabs > pack ? slabs : pack;
+  return dp == nullptr ? REHR_EINVAL : thin5_workspace_bytes(*dp, F32);
 }
 
 extern "C" int rehr_conv5_thin_f32_supported(const rehr_direct_conv_desc* d) {
-  return d != nullptr && thinf_shape_ok(*d) ? 1 : 0;
+  return d != nullptr && thin5_shape_ok(*d, F32) ? 1 : 0;
 }
-
-#define TF_SWITCH(KERNEL, THREADS_OF)                                                                               \
-  switch (d.Wi / 32) {                                                                                              \
-    case 1: TF_LAUNCH(KERNEL, 1, THREADS_OF(1)); break;                                                             \
-    case 2: TF_LAUNCH(KERNEL, 2, THREADS_OF(2)); break;                                                             \
-    case 3: TF_LAUNCH(KERNEL, 3, THREADS_OF(3)); break;                                                             \
-    case 4: TF_LAUNCH(KERNEL, 4, THREADS_OF(4)); break;                                                             \
-    default: return REHR_ENOSUP;                                                                                    \
-  }
-#define TF_LAUNCH(KERNEL, NT_, THREADS)                                                                             \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL<NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)smem);                                                                           \
-    hipLaunchKernelGGL(KERNEL<NT_>, dim3((unsigned)blocks), dim3(THREADS), smem, st, p);                            \
-  } while (0)
-#define TF_T512(n) 512
-#define TF_T64N(n) (128 * (n))
 
 extern "C" int rehr_conv5_thin_fwd_f32(const rehr_direct_conv_desc* dp, void* workspace, int64_t workspace_bytes,
                                        void* stream) {
-  if (dp == nullptr || dp->x == nullptr || dp->w == nullptr || dp->y == nullptr || workspace == nullptr) return REHR_EINVAL;
+  if (dp == nullptr || dp->x == nullptr || dp->w == nullptr || dp->y == nullptr) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
-  if (!thinf_shape_ok(d)) return REHR_ENOSUP;
-  if (workspace_bytes < rehr_conv5_thin_f32_workspace_bytes(dp) || d.act != REHR_ACT_NONE || d.stats_mode != 0) return REHR_EINVAL;
+  if (const int rc = thin5_admit(d, workspace, workspace_bytes, F32)) return rc;
+  if (d.act != REHR_ACT_NONE || d.stats_mode != 0) return REHR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(thinf_pack_fwd_kernel, dim3((TF_NW_FWD * 64 + 255) / 256), dim3(256), 0, st, d.w,
                      reinterpret_cast<float*>(workspace));
@@ -627,20 +548,19 @@ extern "C" int rehr_conv5_thin_fwd_f32(const rehr_direct_conv_desc* dp, void* wo
   p.x = d.x; p.ldx = d.ldx; p.N = d.N; p.D = d.Di; p.H = d.Hi; p.W = d.Wi;
   p.wfrag = reinterpret_cast<const float*>(workspace);
   p.bias = d.bias; p.y = d.y; p.ldy = d.ldy;
-  thinf_segments(d, p.nstrip, p.dseg, p.nseg);
-  const int64_t blocks = (int64_t)d.N * p.nstrip * p.nseg;
-  const size_t smem = (size_t)2 * TF_ROWS * d.Wi * 32 + (size_t)2 * TF_BH * (d.Wi + 4) * TF_PP * 4;
-  TF_SWITCH(thinf_fwd_kernel, TF_T512)
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  const int64_t blocks = thin5_segments(d, p.nstrip, p.dseg, p.nseg);
+  const size_t smem = (size_t)2 * T5_ROWS * d.Wi * 32 + (size_t)2 * T5_BH * (d.Wi + 4) * T5_PP * 4;
+  return thin5_for_width<4>(d.Wi / 32, [&](auto n) {
+    return thin5_launch(thinf_fwd_kernel<decltype(n)::value>, blocks, 512, smem, st, p);
+  });
 }
 
 extern "C" int rehr_conv5_thin_dgrad_f32(const rehr_direct_conv_desc* dp, float* dx, int32_t lddx, void* workspace,
                                          int64_t workspace_bytes, void* stream) {
-  if (dp == nullptr || dp->w == nullptr || dp->y == nullptr || dx == nullptr || workspace == nullptr) return REHR_EINVAL;
+  if (dp == nullptr || dp->w == nullptr || dp->y == nullptr || dx == nullptr) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
-  if (!thinf_shape_ok(d)) return REHR_ENOSUP;
-  if (workspace_bytes < rehr_conv5_thin_f32_workspace_bytes(dp) || lddx < TF_CIN || lddx % 4) return REHR_EINVAL;
+  if (const int rc = thin5_admit(d, workspace, workspace_bytes, F32)) return rc;
+  if (lddx < T5_CIN || lddx % 4) return REHR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(thinf_pack_dgrad_kernel, dim3((TF_NW_DG * 64 + 255) / 256), dim3(256), 0, st, d.w,
                      reinterpret_cast<float*>(workspace));
@@ -648,31 +568,26 @@ extern "C" int rehr_conv5_thin_dgrad_f32(const rehr_direct_conv_desc* dp, float*
   p.dy = d.y; p.ldy = d.ldy; p.N = d.N; p.D = d.Di; p.H = d.Hi; p.W = d.Wi;
   p.wfrag = reinterpret_cast<const float*>(workspace);
   p.dx = dx; p.lddx = lddx;
-  thinf_segments(d, p.nstrip, p.dseg, p.nseg);
-  const int64_t blocks = (int64_t)d.N * p.nstrip * p.nseg;
-  const size_t smem = (size_t)TF_RING * TF_ROWS * (d.Wi + TF_PADW) * 8;
-  TF_SWITCH(thinf_dgrad_kernel, TF_T512)
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  const int64_t blocks = thin5_segments(d, p.nstrip, p.dseg, p.nseg);
+  const size_t smem = (size_t)T5_RING * T5_ROWS * (d.Wi + T5_PADW) * 8;
+  return thin5_for_width<4>(d.Wi / 32, [&](auto n) {
+    return thin5_launch(thinf_dgrad_kernel<decltype(n)::value>, blocks, 512, smem, st, p);
+  });
 }
 
 extern "C" int rehr_conv5_thin_wgrad_f32(const rehr_direct_conv_desc* dp, float* dw, float* dbias, void* workspace,
                                          int64_t workspace_bytes, void* stream) {
-  if (dp == nullptr || dp->x == nullptr || dp->y == nullptr || dw == nullptr || workspace == nullptr) return REHR_EINVAL;
+  if (dp == nullptr || dp->x == nullptr || dp->y == nullptr || dw == nullptr) return REHR_EINVAL;
   const rehr_direct_conv_desc& d = *dp;
-  if (!thinf_shape_ok(d)) return REHR_ENOSUP;
-  if (workspace_bytes < rehr_conv5_thin_f32_workspace_bytes(dp)) return REHR_EINVAL;
+  if (const int rc = thin5_admit(d, workspace, workspace_bytes, F32)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ThinF32WgradParams p;
   p.x = d.x; p.dy = d.y; p.ldx = d.ldx; p.ldy = d.ldy; p.N = d.N; p.D = d.Di; p.H = d.Hi; p.W = d.Wi;
   p.slabs = reinterpret_cast<float*>(workspace);
-  thinf_segments(d, p.nstrip, p.dseg, p.nseg);
-  const int64_t blocks = (int64_t)d.N * p.nstrip * p.nseg;
-  const size_t smem = (size_t)2 * TF_BH * (d.Wi + 4) * 64 + (size_t)TF_RING * TF_ROWS * 2 * (d.Wi * 4 + 16);
-  TF_SWITCH(thinf_wgrad_kernel, TF_T64N)
-  REHR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(thinf_wgrad_reduce_kernel, dim3((2 * TF_CIN * 125 + 2 + 31) / 32), dim3(256), 0, st, p.slabs,
-                     (int)blocks, dw, dbias);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  const int64_t blocks = thin5_segments(d, p.nstrip, p.dseg, p.nseg);
+  const size_t smem = (size_t)2 * T5_BH * (d.Wi + 4) * 64 + (size_t)T5_RING * T5_ROWS * 2 * (d.Wi * 4 + 16);
+  const int rc = thin5_for_width<4>(d.Wi / 32, [&](auto n) {   // two waves per 32 voxels of the row
+    return thin5_launch(thinf_wgrad_kernel<decltype(n)::value>, blocks, 128 * decltype(n)::value, smem, st, p);
+  });
+  return rc != REHR_OK ? rc : thin5_wgrad_reduce(p.slabs, (int)blocks, dw, dbias, st);
 }

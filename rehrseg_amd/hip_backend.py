@@ -540,9 +540,23 @@ def _direct_desc(x, w, bias, y, stride, pad, act, slope, stats, stats_mode):
     return d
 
 
-def small_cin_bf16_out_ok(w_shape, stride):
+def _shape_desc(x_shape, w_shape, stride, pad):
+    """A descriptor without pointers, for the library's questions about a shape: dense NDHWC tensors, the output extent
+    the convolution gives."""
+    d = L.DirectConvDesc()
+    d.N, d.Cin, d.Di, d.Hi, d.Wi = x_shape
+    d.Cout, _, d.KD, d.KH, d.KW = w_shape
+    d.ldx, d.ldy = d.Cin, d.Cout
+    d.sd, d.sh, d.sw = stride
+    d.pd, d.ph, d.pw = pad
+    d.Do, d.Ho, d.Wo = ((i + 2 * p - k) // s + 1 for i, k, s, p in zip(x_shape[2:], w_shape[2:], stride, pad))
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def small_cin_bf16_out_ok(x_shape, w_shape, stride, pad):
     """Shapes whose thin-input forward runs on the matrix cores (thin_cin_conv.hip) and can therefore store bf16."""
-    return w_shape[1] <= 2 and w_shape[0] in (32, 64) and w_shape[4] <= 8 and stride[2] in (1, 2)
+    return bool(L.load().rehr_conv_small_cin_fwd_on_mfma(C.byref(_shape_desc(x_shape, w_shape, stride, pad))))
 
 
 def small_cin_fwd(x, w, bias, y, stride, pad, act, slope, stats, stats_mode):
@@ -578,11 +592,10 @@ def small_cin_wgrad(x, w, dy, stride, pad, want_bias):
     """dy fp32, or bf16 (mixed precision) where the matrix-core kernel takes the shape (else cast up first)."""
     _chk_dev(x, w, dy)
     lib = L.load()
-    if dy.dtype == torch.bfloat16:
-        d = _direct_desc(x, w.contiguous(), None, dy, stride, pad, 0, 0.0, None, 0)
-        if not lib.rehr_conv_small_cin_wgrad_on_mfma(C.byref(d)):
-            dy = dy.float()
     d = _direct_desc(x, w.contiguous(), None, dy, stride, pad, 0, 0.0, None, 0)
+    if dy.dtype == torch.bfloat16 and not lib.rehr_conv_small_cin_wgrad_on_mfma(C.byref(d)):
+        dy = dy.float()
+        d.y = _ptr(dy)
     nbytes = lib.rehr_conv_small_cin_wgrad_workspace_bytes(C.byref(d))
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     dw = torch.empty_like(w, memory_format=torch.contiguous_format)
@@ -1325,15 +1338,21 @@ def _thin5_ws(d, dev, f32=False):
 USE_THIN5_F32 = True   # sr_head.2 of the fp32 path on the fp32 matrix cores (False: the VALU kernels of direct_conv.hip)
 
 
+@functools.lru_cache(maxsize=None)
+def _thin5_library_takes(x_shape, w_shape, pad, dtype):
+    if dtype not in (torch.bfloat16, torch.float32) or len(w_shape) != 5 or w_shape[1] != x_shape[1]:
+        return False
+    lib = L.load()
+    fn = lib.rehr_conv5_thin_supported if dtype == torch.bfloat16 else lib.rehr_conv5_thin_f32_supported
+    return bool(fn(C.byref(_shape_desc(x_shape, w_shape, (1, 1, 1), pad))))
+
+
 def thin5_supported(x_shape, w_shape, pad, dtype=torch.bfloat16):
-    """Conv3d(16 -> 2, 5x5x5, stride 1, pad 2) with W % 32 == 0 and W <= 160 (bf16) / 128 (fp32): the shapes the
-    matrix-core kernels of thin_conv_{bf16,f32}.hip take."""
-    N, Cin, D, H, W = x_shape
+    """The shapes the matrix-core kernels of thin_conv_{bf16,f32}.hip take, as the library says (remembered per shape:
+    fused_conv3d asks at every call of a thin layer)."""
     if dtype == torch.float32 and not USE_THIN5_F32:
         return False
-    es, wmax = (2, 160) if dtype == torch.bfloat16 else (4, 128)
-    return (tuple(w_shape) == (2, 16, 5, 5, 5) and Cin == 16 and tuple(pad) == (2, 2, 2) and W % 32 == 0
-            and 32 <= W <= wmax and D * H * W * 16 * es < 2 ** 32 and dtype in (torch.bfloat16, torch.float32))
+    return _thin5_library_takes(tuple(x_shape), tuple(w_shape), tuple(pad), dtype)
 
 
 def thin5_fwd(x, w, bias):

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("REHRSEG_HIP_LIB") or os.path.join(_HERE, "librehrseg_
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rehrseg_hip.h")
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 GG_Y_F32 = 1            # rehr_gather_gemm_desc.flags
 GG_WS_READY = 2
 GG_WS_ONLY = 4
@@ -129,6 +129,7 @@ PROTOTYPES = {
     "rehr_im2col_f32": (C.c_int, [_P_DC, _vp, _i32, _vp]),
     "rehr_conv_small_cin_wgrad_workspace_bytes": (_i64, [_P_DC]),
     "rehr_conv_small_cin_wgrad_on_mfma": (C.c_int, [_P_DC]),
+    "rehr_conv_small_cin_fwd_on_mfma": (C.c_int, [_P_DC]),
     "rehr_conv_small_cin_fwd_ybf16": (C.c_int, [_P_DC, _vp]),
     "rehr_conv_small_cin_wgrad_dybf16": (C.c_int, [_P_DC, _vp, _vp, _vp, _i64, _vp]),
     "rehr_conv_small_cin_wgrad_f32": (C.c_int, [_P_DC, _vp, _vp, _vp, _i64, _vp]),

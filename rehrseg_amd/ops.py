@@ -302,7 +302,7 @@ def conv_forward(x1, x2, w, bias, cfg: ConvCfg, act, slope, stats_mode):
         # pass over the network's largest activation); statistics from the fp32 accumulators
         okw = {}
         if (_mixed and not cfg.y_fp32 and x1.dtype == torch.float32 and hasattr(be, "small_cin_bf16_out_ok") and
-                be.small_cin_bf16_out_ok(tuple(w.shape), cfg.stride)):
+                be.small_cin_bf16_out_ok(tuple(x1.shape), tuple(w.shape), tuple(cfg.stride), tuple(cfg.pad))):
             okw["dtype"] = torch.bfloat16
         y = be.new_act(N, Cout, *out_dims, like=x1, **okw)
         be.small_cin_fwd(x1, w, bias, y, cfg.stride, cfg.pad, act, slope, stats, stats_mode)
@@ -570,8 +570,7 @@ class _FusedConv(torch.autograd.Function):
             be.add_channel_const(dz, k)
         else:
             db_in = None
-            if (has_b and ctx.needs_input_grad[3] and y0.dtype == torch.bfloat16 and not cfg.transposed and
-                    hasattr(be, "small_cin_bf16_out_ok")):
+            if has_b and ctx.needs_input_grad[3] and y0.dtype == torch.bfloat16 and not cfg.transposed:
                 # mixed precision: the conv-bias gradient (column sums of dz) rides on the InstanceNorm apply pass
                 dz, dp1, dp2, db_in = be.instnorm_act_bwd(dy, y0, mr, p1, p2, cfg.act, cfg.slope, want_conv_bias=True)
             else:

@@ -361,6 +361,37 @@ def test_thin_input_layers_store_bf16_directly(Cin, Cout, K, stride, pad):
     assert torch.equal(dw16, dw32) and torch.equal(db16, db32)
 
 
+def test_thin_input_layer_without_a_matrix_core_forward_stays_fp32_in_mixed_precision():
+    """Conv3d(2 -> 64, 5x7x7): the weights (143 360 B) and the patch do not fit the matrix-core forward's 150 KB of LDS,
+    so only the fp32 vector kernel takes the layer.  Under mixed_precision() it is the same kernel on the same operands
+    (the library, not a shape rule in Python, says that no bf16 store is on offer; the call used to raise): float32,
+    bitwise equal.  The extents leave partial tiles in H and W.
+    The weight gradient of this layer is not hb.small_cin_wgrad's (62 taps per wave: its vector kernel declines, as its
+    matrix-core kernel does) but conv_wgrad's im2col + GEMM route, which casts a bf16 dY up first: bitwise the fp32 call."""
+    from test_kernels_gpu import TOL, _close
+    g = torch.Generator().manual_seed(41)
+    stride, pad = (1, 1, 1), (2, 3, 3)
+    x = torch.randn(1, 2, 3, 6, 20, generator=g).to(DEV).contiguous(memory_format=torch.channels_last_3d)
+    w = (torch.randn(64, 2, 5, 7, 7, generator=g) / 490 ** 0.5).to(DEV)
+    b = torch.randn(64, generator=g).to(DEV)
+    y32 = ops.fused_conv3d(x, w, b, stride, pad)
+    with ops.mixed_precision():
+        ymp = ops.fused_conv3d(x, w, b, stride, pad)
+    assert ymp.dtype == torch.float32 and y32.dtype == torch.float32
+    assert torch.equal(ymp, y32)
+    _close(y32, F.conv3d(x.double().cpu(), w.double().cpu(), b.double().cpu(), stride, pad), TOL)
+    cfg = ops.ConvCfg(stride, pad, False)
+    dy = torch.randn(y32.shape, generator=g).to(DEV).to(torch.bfloat16).contiguous(memory_format=torch.channels_last_3d)
+    dw16, db16 = ops.conv_wgrad(dy, x, None, w, cfg, True)
+    dw32, db32 = ops.conv_wgrad(dy.float(), x, None, w, cfg, True)
+    assert torch.equal(dw16, dw32) and torch.equal(db16, db32)
+    wr = w.double().cpu().requires_grad_()
+    br = b.double().cpu().requires_grad_()
+    rw, rb = torch.autograd.grad(F.conv3d(x.double().cpu(), wr, br, stride, pad), [wr, br], dy.double().cpu())
+    _close(dw16, rw, TOL)
+    _close(db16, rb, TOL)
+
+
 def test_teacher_window_stem_in_mixed_precision_stores_bf16():
     """encoder_on_windows under mixed_precision(): the per-slice stem responses stay fp32 (they are combined linearly),
     the assembled windows are stored as bf16 -- exactly the fp32 assembly rounded."""

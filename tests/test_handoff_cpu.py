@@ -68,7 +68,7 @@ def test_new_symbols_are_declared_and_exported():
     declared = L.declared_symbols()
     for s in NEW_SYMBOLS:
         assert s in declared and s in L.PROTOTYPES and hasattr(lib, s), s
-    assert L.ABI_VERSION == 5 and lib.rehr_abi_version() == 5
+    assert L.ABI_VERSION == 6 and lib.rehr_abi_version() == 6
 
 
 def test_new_entry_points_reject_null_arguments_without_launching():
