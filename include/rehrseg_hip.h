@@ -141,6 +141,17 @@ typedef struct {
 
 /* scratch bytes the Winograd path needs for this descriptor; 0 = not applicable */
 int64_t rehr_gather_gemm_wino_bytes(const rehr_gather_gemm_desc* d);
+/* Which fp32 Winograd kernel a launch of this descriptor with that scratch takes: the route in the low byte
+ * (0 exactly when rehr_gather_gemm_wino_bytes is 0), the variant in bits 8..15 -- FLAT8: 1 / 2 for 32 / 64 tiles per
+ * block, W32P: 1 / 2 for 256- / 512-thread blocks, else 0.  Reads no pointer of the descriptor. */
+#define REHR_GG_ROUTE_NONE 0
+#define REHR_GG_ROUTE_FLAT8 1    /* F(2x2,3x3), flattened tiles (small planes) */
+#define REHR_GG_ROUTE_W32P 2     /* F(2x2,3x3), 32-channel pipelined tile */
+#define REHR_GG_ROUTE_BIG8 3     /* F(2x2,3x3), 16 x 16 regions x 64 channels */
+#define REHR_GG_ROUTE_SMALL 4    /* F(2x2,3x3), 8 x 16 regions x 32 channels */
+#define REHR_GG_ROUTE_FLAT22 5   /* F(2x2,2x2), flattened tiles */
+#define REHR_GG_ROUTE_REGION22 6 /* F(2x2,2x2), 16 x 16 regions */
+int rehr_gather_gemm_wino_route(const rehr_gather_gemm_desc* d);
 int rehr_gather_gemm_f32(const rehr_gather_gemm_desc* d, void* stream);
 /* The stride phases of ONE layer (same x1/x2, wp, y, N, Npad; count <= 8), differing
  * only in lattice, taps and destination offset, in a single grid.                   */

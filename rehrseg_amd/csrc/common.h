@@ -40,6 +40,18 @@ int set_dyn_lds_once(int bytes) {
   }
   return REHR_OK;
 }
+// The same for a kernel whose dynamic LDS depends on the problem: the limit only ever grows.
+template <auto KERN>
+int grow_dyn_lds(size_t bytes) {
+  static size_t attr_bytes = 0;
+  if (bytes > attr_bytes) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
+        hipSuccess)
+      return REHR_EHIP;
+    attr_bytes = bytes;
+  }
+  return REHR_OK;
+}
 
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher places on
 // the same XCD (b % 8 equal) become consecutive logical ids, so neighbouring

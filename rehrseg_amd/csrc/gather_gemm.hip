@@ -23,9 +23,8 @@
 //    sum-of-squares that SEGating's pool and InstanceNorm3d need (double
 //    atomics, one per channel per wave).
 #include "common.h"
-#include "gg_shared.h"
 #include "halo_conv.h"
-#include "wino_conv.h"
+#include "wino_shared.h"
 
 namespace {
 
@@ -376,6 +375,34 @@ int launch_generic(const GGMulti& pm, int count, hipStream_t st) {
 
 }  // namespace
 
+// The one route decision of the fp32 Winograd family, in this order: the flattened-tile F(2x2,3x3) kernel (small planes),
+// the F(2x2,3x3) region kernels (32-channel pipelined tile, big tile, small tile: wino_region_plan), then the
+// F(2x2,2x2) kernels, flattened tiles before regions.  REHR_DBG_GG_NO_FLAT8 takes both flattened-tile kernels out
+// (wino22_flat_plan looks at it itself: the multi-part entry plans through it as well).  Reads no pointer.
+WinoRoute wino_route(const rehr_gather_gemm_desc& d, WinoPlan& plan) {
+  if (!(d.debug_flags & REHR_DBG_GG_NO_FLAT8) && wino_flat8_plan(d, plan)) return WINO_FLAT8;
+  if (const WinoRoute r = wino_region_plan(d, plan)) return r;
+  if (wino22_flat_plan(d, plan, 1)) return WINO_FLAT22;
+  if (wino22_region_plan(d, plan)) return WINO_REGION22;
+  plan.bytes = 0;
+  return WINO_NONE;
+}
+
+// The weight transforms of the `count` parts that share the launch, then the launch.  REHR_GG_WS_ONLY ends here, right
+// behind the transforms, for every kernel of the family.
+static int wino_run(WinoRoute r, const rehr_gather_gemm_desc* ds, int count, const WinoPlan& plan, hipStream_t st) {
+  for (int i = 0; i < count; ++i) {
+    const int rc = r >= WINO_FLAT22 ? wino22_weights_launch(ds[i], plan, st) : wino_weights_launch(r, ds[i], plan, st);
+    if (rc != REHR_OK) return rc;
+  }
+  if (ds[0].flags & REHR_GG_WS_ONLY) return REHR_OK;
+  switch (r) {
+    case WINO_FLAT8: return wino_flat8_launch(ds[0], plan, st);
+    case WINO_W32P: case WINO_BIG8: case WINO_SMALL: return wino_region_launch(r, ds, count, plan, st);
+    default: return wino22_launch(r, ds, count, plan, st);
+  }
+}
+
 extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, int32_t count, void* stream) {
   if (descs == nullptr || count < 1 || count > MAX_PHASES) return REHR_EINVAL;
   for (int i = 0; i < count; ++i) {
@@ -388,8 +415,8 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
     // (Cin and c1 may differ as well, unlike in rehr_gather_gemm_multi_bf16: the K step is 32 channels for every phase)
   }
   hipStream_t st = (hipStream_t)stream;
-  // REHR_GG_WS_ONLY: the weight transforms of this call and nothing else (every Winograd try-function below returns
-  // right behind its transform launch; whatever no Winograd kernel takes has nothing to prepare)
+  // REHR_GG_WS_ONLY: the weight transforms of this call and nothing else (wino_run; whatever no Winograd kernel takes
+  // has nothing to prepare)
   const bool ws_only = (descs[0].flags & REHR_GG_WS_ONLY) != 0;
   for (int i = 1; i < count; ++i)
     if ((descs[i].flags ^ descs[0].flags) & (REHR_GG_WS_ONLY | REHR_GG_WS_READY)) return REHR_EINVAL;
@@ -397,16 +424,14 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
     const int trc = tconv_ks_try(descs, count, false, st);
     if (trc != REHR_ENOSUP) return trc;
   }
-  if (count > 1 && descs[0].wino_ws != nullptr && (descs[0].td.count > 3 || descs[0].td.count == 1)) {
-    // tap-range parts of a split-K launch (many depth taps; or the single depth taps of a layer whose plain Winograd
-    // grid would leave half the chip idle): all parts in one Winograd grid, or none
-    const int src = wino_conv_split_try(descs, count, st);
-    if (src != REHR_ENOSUP) return src;
-  }
-  if (count > 1 && descs[0].wino_ws != nullptr && descs[0].td.count <= 3) {
-    // output phases of a transposed convolution on small planes: one grid of the flattened-tile F(2x2,2x2) kernel
-    const int frc = wino22_flat_multi_try(descs, count, st);
-    if (frc != REHR_ENOSUP) return frc;
+  WinoPlan plan{};
+  if (count > 1 && descs[0].wino_ws != nullptr) {
+    // All parts in one Winograd grid, or none.  Tap-range parts of a split-K launch (many depth taps; or the single
+    // depth taps of a layer whose plain Winograd grid would leave half the chip idle): the big-tile kernel.  Output
+    // phases of a transposed convolution on small planes: the flattened-tile F(2x2,2x2) kernel.
+    const int taps = descs[0].td.count;
+    if ((taps > 3 || taps == 1) && wino_split_plan(descs, count, plan)) return wino_run(WINO_BIG8, descs, count, plan, st);
+    if (taps <= 3 && wino22_flat_multi_plan(descs, count, plan)) return wino_run(WINO_FLAT22, descs, count, plan, st);
   }
   GGMulti pm;
   pm.interleave = 0;
@@ -418,11 +443,13 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
     // launch (many depth taps, few tiles): one Winograd launch per part would run them one after the other on a
     // quarter of the chip, the generic kernel runs all parts in one grid
     if (descs[i].wino_ws != nullptr && !(count > 1 && descs[i].td.count > 3)) {
-      int wrc = wino_flat8_conv_try(descs[i], st);
-      if (wrc == REHR_ENOSUP) wrc = wino_conv_try(descs[i], st);
-      if (wrc == REHR_ENOSUP) wrc = wino22_conv_try(descs[i], st);
-      if (wrc == REHR_OK) continue;
-      if (wrc != REHR_ENOSUP) return wrc;
+      const WinoRoute r = wino_route(descs[i], plan);
+      // (a scratch that is too small or misaligned is no error: the direct kernels below take the descriptor)
+      if (r != WINO_NONE && wino_ws_ok(descs[i], plan.bytes)) {
+        const int wrc = wino_run(r, &descs[i], 1, plan, st);
+        if (wrc != REHR_OK) return wrc;
+        continue;
+      }
     }
     if (ws_only) continue;
     if (descs[i].tile_d >= 0) {  // the halo-tile kernel takes what it is good at, one launch each
@@ -439,11 +466,16 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
 }
 
 extern "C" int64_t rehr_gather_gemm_wino_bytes(const rehr_gather_gemm_desc* dp) {
-  if (dp == nullptr || validate(*dp) != REHR_OK) return 0;
-  int64_t b = wino_flat8_workspace_bytes(*dp);
-  if (b == 0) b = wino_workspace_bytes(*dp);
-  if (b == 0) b = wino22_workspace_bytes(*dp);
-  return b;
+  WinoPlan plan{};
+  if (dp == nullptr || validate(*dp) != REHR_OK || wino_route(*dp, plan) == WINO_NONE) return 0;
+  return plan.bytes;
+}
+
+extern "C" int rehr_gather_gemm_wino_route(const rehr_gather_gemm_desc* dp) {
+  WinoPlan plan{};
+  if (dp == nullptr || validate(*dp) != REHR_OK) return REHR_GG_ROUTE_NONE;
+  const WinoRoute r = wino_route(*dp, plan);
+  return r == WINO_NONE ? REHR_GG_ROUTE_NONE : (int)r | (plan.variant << 8);
 }
 
 extern "C" int rehr_gather_gemm_f32(const rehr_gather_gemm_desc* dp, void* stream) {

@@ -19,7 +19,6 @@
 //    in the fp32 kernel.
 #include "common.h"
 #include "gg_shared.h"
-#include "wino_conv.h"
 
 int halo_conv_bf16_try(const rehr_gather_gemm_desc& d, hipStream_t stream);  // halo_conv_bf16.hip
 

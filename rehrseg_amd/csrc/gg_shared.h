@@ -135,3 +135,7 @@ int gg_launch(const GGMulti& pm, int count, hipStream_t stream) {
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }
+
+// kernel == stride transposed convolution, fp32 and bf16: all stride phases of a 128-voxel input tile in one block
+// (tconv_ks.hip).  REHR_ENOSUP: not a shape for it.
+int tconv_ks_try(const rehr_gather_gemm_desc* ds, int count, bool bf16, hipStream_t stream);

@@ -17,27 +17,19 @@
 //   schedule = three waves per SIMD hide each other's LDS latency; weights one k-group ahead in
 //              registers, next patch fetched at the top of an item, one barrier per item
 #include "common.h"
-#include "gg_shared.h"
-#include "wino_conv.h"
-#include "wino22_shared.h"
+#include "wino_shared.h"
 #include <cstdlib>
 
 namespace {
 
-constexpr int LD = 36;                 // floats per voxel slot (32 channels + 4)
+constexpr int LD = WINO_LDX;           // floats per voxel slot (32 channels + 4)
 constexpr int PW = 17;                 // patch is 17 x 17
 constexpr int RP = PW * LD + 12;       // row pitch: two rows = 32 floats mod 64
 constexpr int BUF = PW * RP;           // floats per slice buffer
 constexpr int PVOX = PW * PW;          // 289
 constexpr int NT_ = 768;               // threads: 12 waves
 constexpr int NX = (PVOX * 8 + NT_ - 1) / NT_;  // 4 pieces per thread
-constexpr int MAXPH = 4;
-
-struct Phase {
-  int sh, sw;      // source stride of the sub-lattice (1 or 2)
-  int ph, pw;      // parity offset inside the source
-  int dh0, dw0;    // sub-lattice position of patch row/col 0 relative to the region origin
-};
+constexpr int MAXPH = WINO_MAXPH;
 
 struct W22Params {
   rehr_gather_gemm_desc d;
@@ -372,7 +364,7 @@ __global__ __launch_bounds__(NT_) void wino22_conv_kernel(const W22Params p) {
 // read in the index space slice * (2 nth + 1) + lattice row -- the organisation of wino_flat8_conv.hip; compute loop,
 // weight panel and summation order are this file's.
 constexpr int F22_NX = 5;        // 16-byte pieces per thread
-constexpr int F22_MAXSLOT = 8;   // slices a block may touch
+constexpr int F22_MAXSLOT = FLAT_MAXSLOT;   // slices a block may touch
 
 struct F22Params {
   rehr_gather_gemm_desc d;
@@ -649,233 +641,111 @@ __global__ __launch_bounds__(NT_) void wino22_flat_conv_kernel(const F22Params p
   }
 }
 
-int f22_conflicts(int ntw, int RPf) {
-  int worst = 0;
-  for (int a = 0; a < ntw; ++a) {
-    int cnt[16] = {0};
-    for (int l = 0; l < 16; ++l) {
-      const int t = a + l, th = t / ntw, tw = t - th * ntw;
-      const int unit = ((tw * LD + th * 2 * RPf) / 4) & 15;
-      if (++cnt[unit] > worst) worst = cnt[unit];
-    }
-  }
-  return worst;
-}
+// 64 tiles per 768-thread block, one block per CU.  Fill threshold: below one full round of 64-tile blocks the padded
+// region kernel (more, equally long blocks) fills the chip better (512->128 @12x12: 144 blocks here against 256 there,
+// 1.21 vs 1.12 ms)
+constexpr FlatConsts F22_CONSTS = {1, 64, F22_NX * NT_, 256, (int64_t)4 * 3 * 2 * 16 * 64,
+                                   (int64_t)F22_MAXSLOT * 12 * 2 * 2 * 32, 160 * 1024};
 
-bool plan22_flat(const rehr_gather_gemm_desc& d, F22Params& p, int parts = 1) {
-  if ((d.debug_flags & REHR_DBG_GG_NO_FLAT8) || d.sd != 1) return false;
+// what both planners ask of the taps: (2-tap, 2-tap) phases or (4-tap, 4-tap) stride-2 gathers; fills phases and scratch
+bool plan22_taps(const rehr_gather_gemm_desc& d, WinoPlan& plan) {
+  if (d.sd != 1) return false;
   AxisPlan ah, aw;
   if (!plan_axis(d.th, d.sh, d.bh, ah) || !plan_axis(d.tw, d.sw, d.bw, aw)) return false;
   if (ah.nph != aw.nph) return false;
   if (ah.nph == 2 && (d.osh != 1 || d.osw != 1 || d.obh || d.obw)) return false;
-  if (d.td.count < 1 || d.td.count > 3) return false;
-  if (d.Npad % 64 || d.Lh < 6 || d.Lw < 6 || d.Lw > 64 || d.Lh > 2048 || d.Ld > 127) return false;
-  if (d.Lh % 16 == 0 && d.Lw % 16 == 0) return false;      // whole regions: the region kernel stages less
-  constexpr int TB = 64;
-  p.d = d;
-  p.nth = (d.Lh + 1) / 2;
-  p.ntw = (d.Lw + 1) / 2;
-  p.tps = p.nth * p.ntw;
-  if ((int64_t)p.nth * 2 * p.ntw * 2 * 10 > (int64_t)d.Lh * d.Lw * 13) return false;
-  const int64_t ntiles = (int64_t)d.N * d.Ld * p.tps;
-  if (ntiles >= (1ll << 30) || ntiles < TB) return false;
-  p.ntiles = (int)ntiles;
-  // one 768-thread block per CU: below one full round of 64-tile blocks the padded region kernel (more, equally long
-  // blocks) fills the chip better (512->128 @12x12: 144 blocks here against 256 there, 1.21 vs 1.12 ms)
-  if ((ntiles + 63) / 64 * (d.Npad / 64) * parts < 256) return false;
-  if ((TB - 2) / p.tps + 2 > F22_MAXSLOT) return false;
-  p.PH = 2 * p.nth + 1;
-  p.nev = p.ntw + 1;
-  p.PWs = 2 * p.ntw + 1;
-  const int trr = (TB - 2) / p.ntw + 2, sdiff = (TB - 2) / p.tps + 1;
-  p.rows = 2 * (trr - 1) + sdiff + 3;
-  if ((int64_t)p.rows * p.PWs * 8 > (int64_t)F22_NX * NT_) return false;
-  p.rowmagic = 65536 / p.PWs + 1;
-  for (int v = 0; v <= p.rows * p.PWs; ++v)
-    if (((v * p.rowmagic) >> 16) != v / p.PWs) return false;
-  int best = 1 << 30;
-  p.rowpad = 12;
-  for (int pad = 4; pad <= 64; pad += 4) {
-    const int c = f22_conflicts(p.ntw, p.PWs * LD + pad);
-    if (c < best) { best = c; p.rowpad = pad; }
-  }
-  p.RP = p.PWs * LD + p.rowpad;
-  p.kchunks = (d.Cin + 31) / 32;
-  p.parts = 1;
-  p.nphase = ah.nph * aw.nph;
-  for (int i = 0; i < ah.nph; ++i)
-    for (int j = 0; j < aw.nph; ++j) {
-      Phase& P = p.phase[i * aw.nph + j];
-      P.sh = ah.stride; P.sw = aw.stride;
-      P.ph = ah.par[i]; P.pw = aw.par[j];
-      P.dh0 = ah.dmin[i]; P.dw0 = aw.dmin[j];
-    }
-  const int64_t need = (int64_t)p.nphase * d.td.count * 9 * d.Npad * p.kchunks * 32 * 4;
-  if (need >= (1ll << 32) - 64) return false;
-  p.up_bytes = (uint32_t)need;
-  if (!gg_src_fits(d, (int64_t)d.N * d.Di * d.Hi * d.Wi, 4)) return false;   // one buffer over the whole batch
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31) || d.Npad / 64 > 65535) return false;
-  const int64_t xfl = (int64_t)2 * (p.rows * p.RP + LD + 4), efl = (int64_t)4 * 3 * 2 * 16 * 64;
-  const int64_t rfl = (int64_t)F22_MAXSLOT * 12 * 2 * 2 * 32;
-  int64_t fl = xfl > efl ? xfl : efl;
-  if (rfl > fl) fl = rfl;
-  p.tab_off = (int)fl;
-  if ((fl + 3 * TB) * 4 > 160 * 1024) return false;
-  return true;
-}
-
-bool plan22(const rehr_gather_gemm_desc& d, W22Params& p) {
-  if (d.sd != 1) return false;
-  AxisPlan ah, aw;
-  if (!plan_axis(d.th, d.sh, d.bh, ah) || !plan_axis(d.tw, d.sw, d.bw, aw)) return false;
-  if (ah.nph != aw.nph) return false;                    // (2-tap, 2-tap) phases or (4-tap, 4-tap) stride-2 gathers
-  if (ah.nph == 2 && (d.osh != 1 || d.osw != 1 || d.obh || d.obw)) return false;
-  if (d.td.count < 1 || d.td.count > 3) return false;
-  if (d.Npad % 64 || d.Lh < 12 || d.Lw < 12) return false;
-  p.nb_h = (d.Lh + 15) / 16;
-  p.nb_w = (d.Lw + 15) / 16;
-  // padding to whole 16 x 16 regions: up to 1.3x always; up to 1.78x (12 x 12, 24 x 24 planes: the reference's own crops)
-  // when the grid still fills the chip -- the padded transform-domain kernel then equals the direct kernel's MFMA count
-  // at a better utilisation
-  const int64_t padded = (int64_t)p.nb_h * 16 * p.nb_w * 16, exact = (int64_t)d.Lh * d.Lw;
-  if (padded * 10 > exact * 13) {
-    if (padded * 100 > exact * 178 || (int64_t)p.nb_h * p.nb_w * d.Ld * d.N * (d.Npad / 64) < 256) return false;
-  }
-  p.d = d;
-  p.kchunks = (d.Cin + 31) / 32;
-  p.nphase = ah.nph * aw.nph;
-  for (int i = 0; i < ah.nph; ++i)
-    for (int j = 0; j < aw.nph; ++j) {
-      Phase& P = p.phase[i * aw.nph + j];
-      P.sh = ah.stride; P.sw = aw.stride;
-      P.ph = ah.par[i]; P.pw = aw.par[j];
-      P.dh0 = ah.dmin[i]; P.dw0 = aw.dmin[j];
-    }
-  const int64_t need = (int64_t)p.nphase * d.td.count * 9 * d.Npad * p.kchunks * 32 * 4;
-  if (need >= (1ll << 32) - 64) return false;
-  p.up_bytes = (uint32_t)need;
-  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return false;
-  if ((int64_t)p.nb_h * p.nb_w * d.Ld >= (1ll << 31) || d.Npad / 64 > 65535 || d.N > 65535) return false;
-  return true;
+  if (d.td.count < 1 || d.td.count > 3 || d.Npad % 64) return false;
+  plan.variant = 0;
+  plan.kchunks = (d.Cin + 31) / 32;
+  plan.nphase = fill_phases(ah, aw, plan.phase);
+  plan.bytes = wino_scratch_bytes(d, 9 * plan.nphase);
+  return plan.bytes != 0;
 }
 
 }  // namespace
 
-int64_t wino22_workspace_bytes(const rehr_gather_gemm_desc& d) {
-  F22Params f;
-  if (plan22_flat(d, f)) return (int64_t)f.up_bytes;
-  W22Params p;
-  return plan22(d, p) ? (int64_t)p.up_bytes : 0;
+bool wino22_flat_plan(const rehr_gather_gemm_desc& d, WinoPlan& plan, int parts) {
+  if (d.debug_flags & REHR_DBG_GG_NO_FLAT8) return false;
+  if (!plan22_taps(d, plan) || d.Lh > 2048 || d.Ld > 127) return false;
+  return plan_flat_geom(d, F22_CONSTS, parts, plan.flat);
 }
 
-static bool f22_allow_smem(size_t smem) {   // the attribute only ever grows
-  static size_t attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute((const void*)wino22_flat_conv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-        hipSuccess)
+bool wino22_region_plan(const rehr_gather_gemm_desc& d, WinoPlan& plan) {
+  if (!plan22_taps(d, plan) || d.Lh < 12 || d.Lw < 12) return false;
+  plan.nb_h = (d.Lh + 15) / 16;
+  plan.nb_w = (d.Lw + 15) / 16;
+  // padding to whole 16 x 16 regions: up to 1.3x always; up to 1.78x (12 x 12, 24 x 24 planes: the reference's own crops)
+  // when the grid still fills the chip -- the padded transform-domain kernel then equals the direct kernel's MFMA count
+  // at a better utilisation
+  const int64_t padded = (int64_t)plan.nb_h * 16 * plan.nb_w * 16, exact = (int64_t)d.Lh * d.Lw;
+  if (padded * 10 > exact * 13) {
+    if (padded * 100 > exact * 178 || (int64_t)plan.nb_h * plan.nb_w * d.Ld * d.N * (d.Npad / 64) < 256) return false;
+  }
+  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return false;
+  return (int64_t)plan.nb_h * plan.nb_w * d.Ld < (1ll << 31) && d.Npad / 64 <= 65535 && d.N <= 65535;
+}
+
+// The output phases of one transposed convolution (same operands and lattice, different taps / output offsets / weight
+// scratch) in one grid of the flattened-tile kernel: plan.phase[part] is the single source phase of each part.
+bool wino22_flat_multi_plan(const rehr_gather_gemm_desc* ds, int count, WinoPlan& plan) {
+  if (count < 2 || count > WINO_MAXPH) return false;
+  if (!wino22_flat_plan(ds[0], plan, count) || plan.nphase != 1) return false;
+  for (int i = 0; i < count; ++i) {
+    WinoPlan q;
+    if (!wino22_flat_plan(ds[i], q, count) || q.nphase != 1 || q.bytes != plan.bytes || !wino_ws_ok(ds[i], q.bytes))
       return false;
-    attr_smem = smem;
+    if (!gg_same_layer(ds[i], ds[0], SAME_DEPTH_TAPS | SAME_DEST) || q.phase[0].sh != plan.phase[0].sh ||
+        q.phase[0].sw != plan.phase[0].sw)
+      return false;
+    plan.phase[i] = q.phase[0];
   }
   return true;
 }
 
-static int wino22_flat_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  F22Params p;
-  if (!plan22_flat(d, p)) return REHR_ENOSUP;
-  if (d.wino_ws_bytes < (int64_t)p.up_bytes || ((uintptr_t)d.wino_ws & 15)) return REHR_ENOSUP;
-  p.up = d.wino_ws;
-  const int64_t total = (int64_t)p.nphase * d.td.count * d.Npad * p.kchunks * 32;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (!(d.flags & REHR_GG_WS_READY)) {
-    hipLaunchKernelGGL(w22_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d, d.wino_ws, p.kchunks);
-    REHR_LAUNCH_CHECK();
-  }
-  if (d.flags & REHR_GG_WS_ONLY) return REHR_OK;
-  const size_t smem = (size_t)(p.tab_off + 3 * 64) * sizeof(float);
-  if (!f22_allow_smem(smem)) return REHR_EHIP;
-  dim3 grid((unsigned)((p.ntiles + 63) / 64), d.Npad / 64, 1);
-  hipLaunchKernelGGL(wino22_flat_conv_kernel, grid, dim3(NT_), smem, stream, p);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+int wino22_weights_launch(const rehr_gather_gemm_desc& d, const WinoPlan& plan, hipStream_t stream) {
+  const int64_t total = (int64_t)plan.nphase * d.td.count * d.Npad * plan.kchunks * 32;
+  return wino_transform_launch<w22_weights_kernel>(d, total, 8192, stream, plan.kchunks);
 }
 
-// The output phases of one transposed convolution (same operands and lattice, different taps / output offsets / weight
-// scratch) in one grid of the flattened-tile kernel.  REHR_OK launched; REHR_ENOSUP not applicable.
-int wino22_flat_multi_try(const rehr_gather_gemm_desc* ds, int count, hipStream_t stream) {
-  if (count < 2 || count > MAXPH) return REHR_ENOSUP;
-  F22Params p;
-  if (!ds[0].wino_ws || !plan22_flat(ds[0], p, count) || p.nphase != 1) return REHR_ENOSUP;
-  const Phase ph0 = p.phase[0];
-  const rehr_gather_gemm_desc& d0 = ds[0];
-  for (int i = 0; i < count; ++i) {
-    const rehr_gather_gemm_desc& d = ds[i];
-    F22Params q;
-    if (!d.wino_ws || ((uintptr_t)d.wino_ws & 15) || !plan22_flat(d, q, count) || q.nphase != 1 ||
-        d.wino_ws_bytes < (int64_t)q.up_bytes || q.up_bytes != p.up_bytes)
-      return REHR_ENOSUP;
-    if (d.x1 != d0.x1 || d.x2 != d0.x2 || d.Cin != d0.Cin || d.c1 != d0.c1 || d.ldx1 != d0.ldx1 || d.ldx2 != d0.ldx2 ||
-        d.Cout != d0.Cout || d.Npad != d0.Npad || d.y != d0.y || d.ldy != d0.ldy || d.N != d0.N || d.Ld != d0.Ld ||
-        d.Lh != d0.Lh || d.Lw != d0.Lw || d.Di != d0.Di || d.Hi != d0.Hi || d.Wi != d0.Wi || d.Dy != d0.Dy ||
-        d.Hy != d0.Hy || d.Wy != d0.Wy || d.osd != d0.osd || d.osh != d0.osh || d.osw != d0.osw || d.obd != d0.obd ||
-        d.bd != d0.bd || d.td.count != d0.td.count || d.td.off0 != d0.td.off0 || d.td.offs != d0.td.offs ||
-        d.bias != d0.bias || d.act != d0.act || d.slope != d0.slope || d.stats != d0.stats ||
-        d.stats_mode != d0.stats_mode || q.phase[0].sh != ph0.sh || q.phase[0].sw != ph0.sw)
-      return REHR_ENOSUP;
-    p.phase[i] = q.phase[0];
-    p.s_up[i] = d.wino_ws;
-    p.s_obh[i] = d.obh;
-    p.s_obw[i] = d.obw;
+int wino22_launch(WinoRoute r, const rehr_gather_gemm_desc* ds, int count, const WinoPlan& plan, hipStream_t stream) {
+  const rehr_gather_gemm_desc& d = ds[0];
+  if (r == WINO_FLAT22) {
+    F22Params p;
+    p.d = d;
+    flat_fill(p, plan.flat);
+    p.kchunks = plan.kchunks;
+    p.nphase = plan.nphase;
+    for (int i = 0; i < WINO_MAXPH; ++i) p.phase[i] = plan.phase[i];
+    p.up_bytes = (uint32_t)plan.bytes;
+    p.parts = count;
+    p.up = count == 1 ? d.wino_ws : nullptr;
+    for (int i = 0; i < count; ++i) {
+      p.s_up[i] = ds[i].wino_ws;
+      p.s_obh[i] = ds[i].obh;
+      p.s_obw[i] = ds[i].obw;
+    }
+    const size_t smem = flat_lds_bytes(plan.flat, 64);
+    const int rc = grow_dyn_lds<wino22_flat_conv_kernel>(smem);
+    if (rc != REHR_OK) return rc;
+    dim3 grid((unsigned)((p.ntiles + 63) / 64), d.Npad / 64, count);
+    hipLaunchKernelGGL(wino22_flat_conv_kernel, grid, dim3(NT_), smem, stream, p);
+  } else {
+    W22Params p;
+    p.d = d;
+    p.nb_h = plan.nb_h;
+    p.nb_w = plan.nb_w;
+    p.kchunks = plan.kchunks;
+    p.nphase = plan.nphase;
+    for (int i = 0; i < WINO_MAXPH; ++i) p.phase[i] = plan.phase[i];
+    p.up = d.wino_ws;
+    p.up_bytes = (uint32_t)plan.bytes;
+    constexpr size_t smem_x = (size_t)2 * BUF * sizeof(float), smem_e = (size_t)4 * 3 * 2 * 16 * 64 * sizeof(float);
+    constexpr size_t smem = smem_x > smem_e ? smem_x : smem_e;
+    const int rc = set_dyn_lds_once<wino22_conv_kernel>((int)smem);
+    if (rc != REHR_OK) return rc;
+    dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d.Ld), d.Npad / 64, d.N);
+    hipLaunchKernelGGL(wino22_conv_kernel, grid, dim3(NT_), smem, stream, p);
   }
-  p.parts = count;
-  p.up = nullptr;
-  for (int i = 0; i < count; ++i) {
-    const int64_t total = (int64_t)ds[i].td.count * ds[i].Npad * p.kchunks * 32;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (!(ds[i].flags & REHR_GG_WS_READY))
-      hipLaunchKernelGGL(w22_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ds[i], ds[i].wino_ws, p.kchunks);
-  }
-  if (d0.flags & REHR_GG_WS_ONLY) {
-    REHR_LAUNCH_CHECK();
-    return REHR_OK;
-  }
-  const size_t smem = (size_t)(p.tab_off + 3 * 64) * sizeof(float);
-  if (!f22_allow_smem(smem)) return REHR_EHIP;
-  dim3 grid((unsigned)((p.ntiles + 63) / 64), d0.Npad / 64, count);
-  hipLaunchKernelGGL(wino22_flat_conv_kernel, grid, dim3(NT_), smem, stream, p);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
-}
-
-int wino22_conv_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  if (d.wino_ws) {
-    const int frc = wino22_flat_try(d, stream);
-    if (frc != REHR_ENOSUP) return frc;
-  }
-  W22Params p;
-  if (!d.wino_ws || !plan22(d, p)) return REHR_ENOSUP;
-  if (d.wino_ws_bytes < (int64_t)p.up_bytes || ((uintptr_t)d.wino_ws & 15)) return REHR_ENOSUP;
-  p.up = d.wino_ws;
-  const int64_t total = (int64_t)p.nphase * d.td.count * d.Npad * p.kchunks * 32;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (!(d.flags & REHR_GG_WS_READY)) {
-    hipLaunchKernelGGL(w22_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d, d.wino_ws, p.kchunks);
-    REHR_LAUNCH_CHECK();
-  }
-  if (d.flags & REHR_GG_WS_ONLY) return REHR_OK;
-  const size_t smem_x = (size_t)2 * BUF * sizeof(float), smem_e = (size_t)4 * 3 * 2 * 16 * 64 * sizeof(float);
-  const size_t smem = smem_x > smem_e ? smem_x : smem_e;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wino22_conv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-        hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
-  dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d.Ld), d.Npad / 64, d.N);
-  hipLaunchKernelGGL(wino22_conv_kernel, grid, dim3(NT_), smem, stream, p);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }

@@ -15,8 +15,7 @@
 //             column ahead.
 //   output  = Y = A^T M A: column combine in registers, row combine across the 4 waves via LDS.
 #include "common.h"
-#include "gg_shared.h"
-#include "wino_conv.h"
+#include "wino_shared.h"
 #include <cstdlib>
 
 namespace {
@@ -1006,8 +1005,9 @@ __global__ __launch_bounds__(256 * G, G == 1 ? 2 : 1) void wino_conv_w32p_kernel
   }
 }
 
-bool w32_ok(const rehr_gather_gemm_desc& d) {
-  if (d.Npad % 64 == 0 || d.Lh < 16 || d.Lw < 16) return false;  // 64-multiples: the big-tile kernel is faster
+// whole 16 x 16 regions tile the plane within 1.3x
+bool regions16_ok(const rehr_gather_gemm_desc& d) {
+  if (d.Lh < 16 || d.Lw < 16) return false;
   const int64_t nb_h = (d.Lh + 15) / 16, nb_w = (d.Lw + 15) / 16;
   return nb_h * 16 * nb_w * 16 * 10 <= (int64_t)d.Lh * d.Lw * 13;
 }
@@ -1019,178 +1019,111 @@ int w32_groups(const rehr_gather_gemm_desc& d) {
 }
 
 template <int G>
-int launch_w32p(const WinoParams& p, const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  const size_t smem_x = (size_t)2 * (W3<2 * G>::BUF + 32) * sizeof(float);
-  const size_t smem_e = (size_t)2 * G * 4 * 2 * 16 * 64 * sizeof(float);
-  const size_t smem = smem_x > smem_e ? smem_x : smem_e;
-  static bool attr_set32p = false;
-  if (!attr_set32p) {
-    if (hipFuncSetAttribute((const void*)wino_conv_w32p_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_set32p = true;
-  }
-  dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d.Ld), d.Npad / 32, d.N);
+int launch_w32p(const WinoParams& p, hipStream_t stream) {
+  constexpr size_t smem_x = (size_t)2 * (W3<2 * G>::BUF + 32) * sizeof(float);
+  constexpr size_t smem_e = (size_t)2 * G * 4 * 2 * 16 * 64 * sizeof(float);
+  constexpr size_t smem = smem_x > smem_e ? smem_x : smem_e;
+  const int rc = set_dyn_lds_once<wino_conv_w32p_kernel<G>>((int)smem);
+  if (rc != REHR_OK) return rc;
+  dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * p.d.Ld), p.d.Npad / 32, p.d.N);
   hipLaunchKernelGGL(wino_conv_w32p_kernel<G>, grid, dim3(256 * G), smem, stream, p);
   return REHR_OK;
 }
 
-bool big_ok(const rehr_gather_gemm_desc& d) {
-  if (d.Npad % 64 || d.Lh < 16 || d.Lw < 16) return false;
-  const int64_t nb_h = (d.Lh + 15) / 16, nb_w = (d.Lw + 15) / 16;
-  return nb_h * 16 * nb_w * 16 * 10 <= (int64_t)d.Lh * d.Lw * 13;
-}
-
 }  // namespace
 
-// fragment-ordered weight transform, shared with wino_flat8_conv.hip
-int wino_weights_frag_launch(const rehr_gather_gemm_desc& d, int kchunks, hipStream_t stream) {
-  if (d.flags & REHR_GG_WS_READY) return REHR_OK;   // the caller kept the transformed weights of an earlier call
-  const int64_t total = (int64_t)d.td.count * d.Npad * kchunks * 32;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(wino_weights_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d, d.wino_ws, kchunks);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
-}
-
-// scratch bytes when the descriptor suits one of the kernels, else 0
-int64_t wino_workspace_bytes(const rehr_gather_gemm_desc& d) {
-  if (d.sd != 1 || d.sh != 1 || d.sw != 1) return 0;
-  if (d.osd != 1 || d.osh != 1 || d.osw != 1 || d.obd || d.obh || d.obw) return 0;
-  if (d.Ld != d.Dy || d.Lh != d.Hy || d.Lw != d.Wy) return 0;
-  if (!three_taps(d.th, d.bh) || !three_taps(d.tw, d.bw)) return 0;
-  if (d.td.count < 1 || d.td.count > 256) return 0;  // depth taps are plain K items (feature_fuse's gradient: 128)
-  if (d.Lh < 8 || d.Lw < 8) return 0;
-  const bool big = big_ok(d) || w32_ok(d);
+// The admission of the three region kernels, and which of them: the 32-channel pipelined tile for Npad = 32, 96, ...
+// (for 64-multiples the big-tile kernel is faster), the big tile, else the small tile when 8 x 16 regions pad the plane
+// by at most 1.34x (24 x 24, 1.333, is in).
+WinoRoute wino_region_plan(const rehr_gather_gemm_desc& d, WinoPlan& plan) {
+  if (d.sd != 1 || d.sh != 1 || d.sw != 1) return WINO_NONE;
+  if (d.osd != 1 || d.osh != 1 || d.osw != 1 || d.obd || d.obh || d.obw) return WINO_NONE;
+  if (d.Ld != d.Dy || d.Lh != d.Hy || d.Lw != d.Wy) return WINO_NONE;
+  if (!three_taps(d.th, d.bh) || !three_taps(d.tw, d.bw)) return WINO_NONE;
+  if (d.td.count < 1 || d.td.count > 256) return WINO_NONE;  // depth taps are plain K items (feature_fuse's gradient: 128)
+  if (d.Lh < 8 || d.Lw < 8) return WINO_NONE;
+  const WinoRoute r = !regions16_ok(d) ? WINO_SMALL : d.Npad % 64 ? WINO_W32P : WINO_BIG8;
   const int64_t nb_h = (d.Lh + 2 * TH - 1) / (2 * TH), nb_w = (d.Lw + 2 * TW - 1) / (2 * TW);
-  if (!big && nb_h * 2 * TH * nb_w * 2 * TW * 100 > (int64_t)d.Lh * d.Lw * 134) return 0;  // 24 x 24 (1.333) is in
-  const int64_t cpad = (int64_t)((d.Cin + 31) / 32) * 32;  // the fragment-order layout pads Cin to 32
-  const int64_t need = (int64_t)d.td.count * 16 * d.Npad * cpad * (int64_t)sizeof(float);
-  if (need >= (1ll << 32) - 64) return 0;
-  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return 0;
-  if (nb_h * nb_w * d.Ld >= (1ll << 31) || d.Npad / 32 > 65535 || d.N > 65535) return 0;
-  return need;
-}
-
-// Split-K parts of one layer (same operands; consecutive depth-tap ranges; one output slab each) in ONE launch of
-// the big-tile kernel.  REHR_OK launched; REHR_ENOSUP not applicable.
-int wino_conv_split_try(const rehr_gather_gemm_desc* ds, int count, hipStream_t stream) {
-  if (count < 2 || count > 8) return REHR_ENOSUP;
-  const rehr_gather_gemm_desc& d0 = ds[0];
-  if (!big_ok(d0) || (int64_t)d0.N * count > 65535) return REHR_ENOSUP;
-  WinoParams p;
-  p.d = d0;
-  p.kchunks = (d0.Cin + 31) / 32;
-  p.dh0 = -1;
-  p.dw0 = -1;
-  p.up = nullptr;
-  p.up_bytes = 0;
-  p.nsplit = count;
-  p.band_major = (d0.debug_flags & REHR_DBG_GG_SLICE_MAJOR) ? 0 : 1;
-  for (int i = 0; i < count; ++i) {
-    const rehr_gather_gemm_desc& d = ds[i];
-    if (!d.wino_ws || ((uintptr_t)d.wino_ws & 15)) return REHR_ENOSUP;
-    const int64_t need = wino_workspace_bytes(d);
-    if (need == 0 || d.wino_ws_bytes < need) return REHR_ENOSUP;
-    // the parts differ in the depth taps and the destination only; no epilogue work (the combine has it)
-    if (d.bias || d.stats_mode || d.act != REHR_ACT_NONE || d.x2 != d0.x2 || d.Cin != d0.Cin || d.c1 != d0.c1 ||
-        d.ldx1 != d0.ldx1 || d.ldx2 != d0.ldx2 || d.Cout != d0.Cout || d.ldy != d0.ldy || d.Ld != d0.Ld ||
-        d.Lh != d0.Lh || d.Lw != d0.Lw || d.Di != d0.Di || d.Hi != d0.Hi || d.Wi != d0.Wi || d.bd != d0.bd ||
-        d.bh != d0.bh || d.bw != d0.bw || d.KH != d0.KH || d.KW != d0.KW || d.th.count != d0.th.count ||
-        d.th.off0 != d0.th.off0 || d.th.offs != d0.th.offs || d.th.k0 != d0.th.k0 || d.th.ks != d0.th.ks ||
-        d.tw.count != d0.tw.count || d.tw.off0 != d0.tw.off0 || d.tw.offs != d0.tw.offs || d.tw.k0 != d0.tw.k0 ||
-        d.tw.ks != d0.tw.ks)
-      return REHR_ENOSUP;
-    p.s_td[i] = d.td;
-    p.s_up[i] = d.wino_ws;
-    p.s_up_bytes[i] = (uint32_t)need;
-    p.s_y[i] = d.y;
-  }
-  for (int i = 0; i < count; ++i) {
-    const int rc = wino_weights_frag_launch(ds[i], p.kchunks, stream);
-    if (rc != REHR_OK) return rc;
-  }
-  if (d0.flags & REHR_GG_WS_ONLY) return REHR_OK;
-  p.nb_h = (d0.Lh + 15) / 16;
-  p.nb_w = (d0.Lw + 15) / 16;
-  const size_t smem_x = (size_t)2 * BUF2 * sizeof(float), smem_e = (size_t)4 * 4 * 2 * 16 * 64 * sizeof(float);
-  const size_t smem = smem_x > smem_e ? smem_x : smem_e;
-  if (hipFuncSetAttribute((const void*)wino_conv_big8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
-      hipSuccess)
-    return REHR_EHIP;
-  dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d0.Ld), d0.Npad / 64, d0.N * count);
-  hipLaunchKernelGGL(wino_conv_big8_kernel, grid, dim3(512), smem, stream, p);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
-}
-
-// REHR_OK launched; REHR_ENOSUP not applicable.
-int wino_conv_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  if (!d.wino_ws) return REHR_ENOSUP;
-  const int64_t need = wino_workspace_bytes(d);
-  if (need == 0 || d.wino_ws_bytes < need || ((uintptr_t)d.wino_ws & 15)) return REHR_ENOSUP;
-  WinoParams p;
-  p.d = d;
-  p.kchunks = (d.Cin + 31) / 32;
-  p.dh0 = -1;
-  p.dw0 = -1;
-  p.up = d.wino_ws;
-  p.up_bytes = (uint32_t)need;
-  p.nsplit = 0;
-  p.band_major = (d.debug_flags & REHR_DBG_GG_SLICE_MAJOR) ? 0 : 1;
-  if (w32_ok(d)) {
-    const int wrc = wino_weights_frag_launch(d, p.kchunks, stream);
-    if (wrc != REHR_OK || (d.flags & REHR_GG_WS_ONLY)) return wrc;
-    const int nfm = w32_groups(d);
-    p.nb_h = (d.Lh + 8 * nfm - 1) / (8 * nfm);
-    p.nb_w = (d.Lw + 15) / 16;
+  if (r == WINO_SMALL && nb_h * 2 * TH * nb_w * 2 * TW * 100 > (int64_t)d.Lh * d.Lw * 134) return WINO_NONE;
+  plan.bytes = wino_scratch_bytes(d, 16);   // the fragment-order layout pads Cin to 32
+  if (plan.bytes == 0) return WINO_NONE;
+  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return WINO_NONE;
+  if (nb_h * nb_w * d.Ld >= (1ll << 31) || d.Npad / 32 > 65535 || d.N > 65535) return WINO_NONE;
+  plan.kchunks = (d.Cin + 31) / 32;
+  plan.variant = 0;
+  plan.nb_h = r == WINO_SMALL ? (int)nb_h : (d.Lh + 15) / 16;
+  plan.nb_w = r == WINO_SMALL ? (int)nb_w : (d.Lw + 15) / 16;
+  if (r == WINO_W32P) {
     // few K items per block (<= 32 input channels): two half-size blocks per CU hide each other's turnover (2 %)
     const bool two = (d.debug_flags & REHR_DBG_GG_W32P_TWO_PER_CU) ? true
                      : (d.debug_flags & REHR_DBG_GG_W32P_ONE_PER_CU) ? false : d.Cin * d.td.count <= 96;
-    const int g = (nfm == 4 && !two) ? 2 : 1;
-    p.nb_h = (d.Lh + 16 * g - 1) / (16 * g);
-    const int rc = g == 2 ? launch_w32p<2>(p, d, stream) : launch_w32p<1>(p, d, stream);
-    if (rc != REHR_OK) return rc;
-    REHR_LAUNCH_CHECK();
-    return REHR_OK;
+    plan.variant = (w32_groups(d) == 4 && !two) ? 2 : 1;
+    plan.nb_h = (d.Lh + 16 * plan.variant - 1) / (16 * plan.variant);
   }
-  if (big_ok(d)) {
-    const int wrc = wino_weights_frag_launch(d, p.kchunks, stream);
-    if (wrc != REHR_OK || (d.flags & REHR_GG_WS_ONLY)) return wrc;
-    p.nb_h = (d.Lh + 15) / 16;
-    p.nb_w = (d.Lw + 15) / 16;
-    const size_t smem_x = (size_t)2 * BUF2 * sizeof(float), smem_e = (size_t)4 * 4 * 2 * 16 * 64 * sizeof(float);
-    const size_t smem = smem_x > smem_e ? smem_x : smem_e;
-    dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d.Ld), d.Npad / 64, d.N);
-    static bool attr_set8 = false;
-    if (!attr_set8) {
-      if (hipFuncSetAttribute((const void*)wino_conv_big8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem) != hipSuccess)
-        return REHR_EHIP;
-      attr_set8 = true;
-    }
-    hipLaunchKernelGGL(wino_conv_big8_kernel, grid, dim3(512), smem, stream, p);
-    REHR_LAUNCH_CHECK();
-    return REHR_OK;
-  }
-  const int64_t nb_h = (d.Lh + 2 * TH - 1) / (2 * TH), nb_w = (d.Lw + 2 * TW - 1) / (2 * TW);
+  return r;
+}
 
-  // weight transform (reads the packed panel, writes the workspace)
-  if (!(d.flags & REHR_GG_WS_READY)) {
-    const int64_t total = (int64_t)d.td.count * d.Npad * d.Cin;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d, d.wino_ws);
-    REHR_LAUNCH_CHECK();
+// Split-K parts of one layer (same operands; consecutive depth-tap ranges; one output slab each) for ONE launch of
+// the big-tile kernel.  plan.bytes is part 0's; every part is admitted against its own size.
+bool wino_split_plan(const rehr_gather_gemm_desc* ds, int count, WinoPlan& plan) {
+  if (count < 2 || count > 8 || (int64_t)ds[0].N * count > 65535) return false;
+  if (wino_region_plan(ds[0], plan) != WINO_BIG8) return false;
+  for (int i = 0; i < count; ++i) {
+    const rehr_gather_gemm_desc& d = ds[i];
+    WinoPlan q{};
+    if (wino_region_plan(d, q) == WINO_NONE || !wino_ws_ok(d, q.bytes)) return false;
+    // the parts differ in the depth taps and the destination only; no epilogue work (the combine has it)
+    if (d.bias || d.stats_mode || d.act != REHR_ACT_NONE || !gg_same_layer(d, ds[0], SAME_HW_TAPS)) return false;
   }
-  if (d.flags & REHR_GG_WS_ONLY) return REHR_OK;
-  p.nb_h = (int)nb_h;
-  p.nb_w = (int)nb_w;
-  const size_t smem_x = (size_t)2 * PVOX * LDX * sizeof(float), smem_e = (size_t)4 * 2 * 16 * 64 * sizeof(float);
-  const size_t smem = smem_x > smem_e ? smem_x : smem_e;
-  dim3 grid((unsigned)(nb_h * nb_w * d.Ld), d.Npad / 32, d.N);
-  hipLaunchKernelGGL(wino_conv_kernel, grid, dim3(256), smem, stream, p);
+  return true;
+}
+
+// fragment-ordered weight transform of the flattened-tile, 32-channel-tile and big-tile kernels; the small tile's own
+int wino_weights_launch(WinoRoute r, const rehr_gather_gemm_desc& d, const WinoPlan& plan, hipStream_t stream) {
+  if (r == WINO_SMALL)
+    return wino_transform_launch<wino_weights_kernel>(d, (int64_t)d.td.count * d.Npad * d.Cin, 4096, stream);
+  return wino_transform_launch<wino_weights_frag_kernel>(d, (int64_t)d.td.count * d.Npad * plan.kchunks * 32, 8192, stream,
+                                                         plan.kchunks);
+}
+
+int wino_region_launch(WinoRoute r, const rehr_gather_gemm_desc* ds, int count, const WinoPlan& plan, hipStream_t stream) {
+  const rehr_gather_gemm_desc& d = ds[0];
+  WinoParams p;
+  p.d = d;
+  p.kchunks = plan.kchunks;
+  p.dh0 = -1;
+  p.dw0 = -1;
+  p.nb_h = plan.nb_h;
+  p.nb_w = plan.nb_w;
+  p.band_major = (d.debug_flags & REHR_DBG_GG_SLICE_MAJOR) ? 0 : 1;
+  // split parts (big tile only): every part with its own taps, transformed weights and slab
+  p.nsplit = count > 1 ? count : 0;
+  p.up = count > 1 ? nullptr : d.wino_ws;
+  p.up_bytes = count > 1 ? 0 : (uint32_t)plan.bytes;
+  for (int i = 0; count > 1 && i < count; ++i) {
+    p.s_td[i] = ds[i].td;
+    p.s_up[i] = ds[i].wino_ws;
+    p.s_up_bytes[i] = (uint32_t)wino_scratch_bytes(ds[i], 16);
+    p.s_y[i] = ds[i].y;
+  }
+  if (r == WINO_W32P) {
+    const int rc = plan.variant == 2 ? launch_w32p<2>(p, stream) : launch_w32p<1>(p, stream);
+    if (rc != REHR_OK) return rc;
+  } else if (r == WINO_BIG8) {
+    constexpr size_t smem_x = (size_t)2 * BUF2 * sizeof(float), smem_e = (size_t)4 * 4 * 2 * 16 * 64 * sizeof(float);
+    constexpr size_t smem = smem_x > smem_e ? smem_x : smem_e;
+    const int rc = set_dyn_lds_once<wino_conv_big8_kernel>((int)smem);
+    if (rc != REHR_OK) return rc;
+    dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d.Ld), d.Npad / 64, d.N * count);
+    hipLaunchKernelGGL(wino_conv_big8_kernel, grid, dim3(512), smem, stream, p);
+  } else {
+    // the small tile needs no raised limit: its dynamic LDS stays under the 64 KB every kernel may use
+    constexpr size_t smem_x = (size_t)2 * PVOX * LDX * sizeof(float), smem_e = (size_t)4 * 2 * 16 * 64 * sizeof(float);
+    constexpr size_t smem = smem_x > smem_e ? smem_x : smem_e;
+    static_assert(smem <= 64 * 1024, "wino_conv_kernel: dynamic LDS beyond the default limit");
+    dim3 grid((unsigned)((int64_t)p.nb_h * p.nb_w * d.Ld), d.Npad / 32, d.N);
+    hipLaunchKernelGGL(wino_conv_kernel, grid, dim3(256), smem, stream, p);
+  }
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }

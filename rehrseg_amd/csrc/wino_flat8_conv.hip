@@ -13,15 +13,14 @@
 // NFM = 2: 512 threads, one block per CU (two waves per SIMD).  NFM = 1: 256 threads, two independent blocks per CU
 // -- half the tiles per block, for layers whose 64-tile block count quantises badly on 256 CUs.
 #include "common.h"
-#include "gg_shared.h"
-#include "wino_conv.h"
+#include "wino_shared.h"
 
 namespace {
 
-constexpr int F8_LDX = 36;   // floats per voxel slot (32 channels + 4)
+constexpr int F8_LDX = WINO_LDX;   // floats per voxel slot (32 channels + 4)
 constexpr int F8_NX = 8;     // 16-byte pieces staged per thread (two halves of 4)
 constexpr int F8_NXH = F8_NX / 2;
-constexpr int F8_MAXSLOT = 8;  // slices a block may touch (statistics slots)
+constexpr int F8_MAXSLOT = FLAT_MAXSLOT;  // slices a block may touch (statistics slots)
 
 struct Flat8Params {
   rehr_gather_gemm_desc d;
@@ -366,124 +365,68 @@ __global__ __launch_bounds__(256 * NFM, NFM == 1 ? 2 : 1) void wino_flat8_conv_k
   }
 }
 
-// LDS bank-group spread of one 16-lane phase of a fragment read: lanes = 16 consecutive tiles at one column parity,
-// 16-byte units (tw * 9 + (row pitch / 2) * tile row) mod 16; returns the worst multiplicity over the alignments
-int f8_conflicts(int ntw, int RP) {
-  int worst = 0;
-  for (int a = 0; a < ntw; ++a) {
-    int cnt[16] = {0};
-    for (int l = 0; l < 16; ++l) {
-      const int t = a + l, th = t / ntw, tw = t - th * ntw;
-      const int unit = ((tw * F8_LDX + th * 2 * RP) / 4) & 15;
-      if (++cnt[unit] > worst) worst = cnt[unit];
-    }
-  }
-  return worst;
+// 32 * nfm tiles per block.  Fill threshold: below ~half a chip of 64 x 64 units the split-K direct path wins.
+FlatConsts flat8_consts(int nfm) {
+  return {2, 32 * nfm, F8_NX * 256 * nfm, 128, (int64_t)nfm * 2 * 4 * 2 * 16 * 64,
+          (int64_t)F8_MAXSLOT * 4 * nfm * 2 * 2 * 2 * 32, (nfm == 1 ? 80 : 160) * 1024};
 }
 
-bool plan_flat8(const rehr_gather_gemm_desc& d, Flat8Params& p, int nfm) {
+bool plan_flat8(const rehr_gather_gemm_desc& d, int nfm, FlatGeom& g) {
   if (d.sd != 1 || d.sh != 1 || d.sw != 1) return false;
   if (d.osd != 1 || d.osh != 1 || d.osw != 1 || d.obd || d.obh || d.obw) return false;
   if (d.Ld != d.Dy || d.Lh != d.Hy || d.Lw != d.Wy) return false;
   if (d.Ld != d.Di || d.Lh != d.Hi || d.Lw != d.Wi) return false;  // "same" convolution: source plane = output plane
   if (!three_taps(d.th, d.bh) || !three_taps(d.tw, d.bw)) return false;
-  if (d.td.count < 1 || d.td.count > 3) return false;
-  if (d.Npad % 64 || d.Lh < 6 || d.Lw < 6 || d.Lw > 64) return false;
-  if (d.Lh % 16 == 0 && d.Lw % 16 == 0) return false;      // whole 16 x 16 regions: the region kernel has less halo
-  const int TB = 32 * nfm, NT_ = 256 * nfm;
-  p.d = d;
-  p.nth = (d.Lh + 1) / 2;
-  p.ntw = (d.Lw + 1) / 2;
-  p.tps = p.nth * p.ntw;
-  if ((int64_t)p.nth * 2 * p.ntw * 2 * 10 > (int64_t)d.Lh * d.Lw * 13) return false;  // odd extents pad a half tile
-  const int64_t ntiles = (int64_t)d.N * d.Ld * p.tps;
-  if (ntiles >= (1ll << 30) || ntiles < TB) return false;
-  p.ntiles = (int)ntiles;
-  // below ~half a chip of 64 x 64 units the split-K direct path wins
-  if ((ntiles + 63) / 64 * (d.Npad / 64) < 128) return false;
-  if ((TB - 2) / p.tps + 2 > F8_MAXSLOT) return false;
-  p.PH = 2 * p.nth + 2;
-  p.nev = p.ntw + 1;
-  p.PWs = 2 * p.nev;
-  const int trr = (TB - 2) / p.ntw + 2, sdiff = (TB - 2) / p.tps + 1;
-  p.rows = 2 * (trr - 1) + 2 * sdiff + 4;
-  if ((int64_t)p.rows * p.PWs * 8 > (int64_t)F8_NX * NT_) return false;
-  p.rowmagic = 65536 / p.PWs + 1;
-  for (int v = 0; v <= p.rows * p.PWs; ++v)
-    if (((v * p.rowmagic) >> 16) != v / p.PWs) return false;
-  int best = 1 << 30;
-  p.rowpad = 8;
-  for (int pad = 4; pad <= 64; pad += 4) {
-    const int c = f8_conflicts(p.ntw, p.PWs * F8_LDX + pad);
-    if (c < best) { best = c; p.rowpad = pad; }
-  }
-  p.RP = p.PWs * F8_LDX + p.rowpad;
-  p.kchunks = (d.Cin + 31) / 32;
-  const int64_t need = (int64_t)d.td.count * 16 * d.Npad * p.kchunks * 32 * 4;
-  if (need >= (1ll << 32) - 64) return false;
-  p.up_bytes = (uint32_t)need;
-  if (!gg_src_fits(d, (int64_t)d.N * d.Di * d.Hi * d.Wi, 4)) return false;   // one buffer over the whole batch
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return false;
-  if (d.Npad / 64 > 65535) return false;
-  const int64_t xfl = (int64_t)2 * (p.rows * p.RP + F8_LDX + 4), efl = (int64_t)nfm * 2 * 4 * 2 * 16 * 64;
-  const int64_t rfl = (int64_t)F8_MAXSLOT * 4 * nfm * 2 * 2 * 2 * 32;
-  int64_t fl = xfl > efl ? xfl : efl;
-  if (rfl > fl) fl = rfl;
-  p.tab_off = (int)fl;
-  const int64_t bytes = (fl + 3 * TB) * 4;
-  if (bytes > (nfm == 1 ? 80 : 160) * 1024) return false;
-  return true;
-}
-
-template <int NFM>
-int launch_flat8(const Flat8Params& p, hipStream_t stream) {
-  constexpr int TB = 32 * NFM;
-  const size_t smem = (size_t)(p.tab_off + 3 * TB) * sizeof(float);
-  static size_t attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute((const void*)wino_flat8_conv_kernel<NFM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-      return REHR_EHIP;
-    attr_smem = smem;
-  }
-  dim3 grid((unsigned)((p.ntiles + TB - 1) / TB), p.d.Npad / 64, 1);
-  hipLaunchKernelGGL(wino_flat8_conv_kernel<NFM>, grid, dim3(256 * NFM), smem, stream, p);
-  return REHR_OK;
+  return plan_flat_geom(d, flat8_consts(nfm), 1, g);
 }
 
 // tiles per block: 64 unless the 64-tile grid leaves a badly filled last round on 256 CUs and the 32-tile one does not
-int f8_pick(const rehr_gather_gemm_desc& d, const Flat8Params& p64) {
+int f8_pick(const rehr_gather_gemm_desc& d, int ntiles) {
   if (d.debug_flags & REHR_DBG_GG_FLAT8_HALF) return 1;
   if (d.debug_flags & REHR_DBG_GG_FLAT8_FULL) return 2;
-  const int64_t units = (int64_t)((p64.ntiles + 63) / 64) * (d.Npad / 64);
+  const int64_t units = (int64_t)((ntiles + 63) / 64) * (d.Npad / 64);
   const double c64 = (double)((units + 255) / 256);             // rounds of one 64-tile block per CU
-  const int64_t u2 = (int64_t)((p64.ntiles + 31) / 32) * (d.Npad / 64), rem = u2 % 512;
+  const int64_t u2 = (int64_t)((ntiles + 31) / 32) * (d.Npad / 64), rem = u2 % 512;
   const double c32 = (double)(u2 / 512) + (rem == 0 ? 0.0 : rem <= 256 ? 0.5 : 1.0);   // two 32-tile blocks per CU
   return (c32 * 1.08 < c64) ? 1 : 2;
 }
 
-}  // namespace
-
-int64_t wino_flat8_workspace_bytes(const rehr_gather_gemm_desc& d) {
-  if (d.debug_flags & REHR_DBG_GG_NO_FLAT8) return 0;
+template <int NFM>
+int launch_flat8(const rehr_gather_gemm_desc& d, const WinoPlan& plan, hipStream_t stream) {
+  constexpr int TB = 32 * NFM;
   Flat8Params p;
-  return plan_flat8(d, p, 2) ? (int64_t)p.up_bytes : 0;
-}
-
-int wino_flat8_conv_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  if ((d.debug_flags & REHR_DBG_GG_NO_FLAT8) || !d.wino_ws) return REHR_ENOSUP;
-  Flat8Params p;
-  if (!plan_flat8(d, p, 2)) return REHR_ENOSUP;
-  if (d.wino_ws_bytes < (int64_t)p.up_bytes || ((uintptr_t)d.wino_ws & 15)) return REHR_ENOSUP;
-  int nfm = f8_pick(d, p);
-  Flat8Params p1;
-  if (nfm == 1 && !plan_flat8(d, p1, 1)) nfm = 2;
-  Flat8Params& q = nfm == 1 ? p1 : p;
-  q.up = d.wino_ws;
-  int rc = wino_weights_frag_launch(d, q.kchunks, stream);
-  if (rc != REHR_OK || (d.flags & REHR_GG_WS_ONLY)) return rc;
-  rc = nfm == 1 ? launch_flat8<1>(q, stream) : launch_flat8<2>(q, stream);
+  p.d = d;
+  flat_fill(p, plan.flat);
+  p.kchunks = plan.kchunks;
+  p.up = d.wino_ws;
+  p.up_bytes = (uint32_t)plan.bytes;
+  const size_t smem = flat_lds_bytes(plan.flat, TB);
+  const int rc = grow_dyn_lds<wino_flat8_conv_kernel<NFM>>(smem);
   if (rc != REHR_OK) return rc;
+  dim3 grid((unsigned)((p.ntiles + TB - 1) / TB), d.Npad / 64, 1);
+  hipLaunchKernelGGL(wino_flat8_conv_kernel<NFM>, grid, dim3(256 * NFM), smem, stream, p);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
+}
+
+}  // namespace
+
+// The 64-tile plan decides admission and scratch size; the 32-tile variant is taken when f8_pick asks for it and its own
+// geometry holds.
+bool wino_flat8_plan(const rehr_gather_gemm_desc& d, WinoPlan& plan) {
+  if (!plan_flat8(d, 2, plan.flat)) return false;
+  plan.bytes = wino_scratch_bytes(d, 16);
+  if (plan.bytes == 0) return false;
+  plan.kchunks = (d.Cin + 31) / 32;
+  plan.variant = f8_pick(d, plan.flat.ntiles);
+  FlatGeom half;
+  if (plan.variant == 1) {
+    if (plan_flat8(d, 1, half)) plan.flat = half;
+    else plan.variant = 2;
+  }
+  return true;
+}
+
+int wino_flat8_launch(const rehr_gather_gemm_desc& d, const WinoPlan& plan, hipStream_t stream) {
+  return plan.variant == 1 ? launch_flat8<1>(d, plan, stream) : launch_flat8<2>(d, plan, stream);
 }

@@ -406,14 +406,32 @@ def _attach_ws(descs, n, needs, sigs, wp):
 
 def _gg_tag(d):
     return (f"N{d.N} {d.Cin}->{d.Cout} lattice {d.Ld}x{d.Lh}x{d.Lw} stride {d.sd}{d.sh}{d.sw} "
-            f"taps {d.td.count}x{d.th.count}x{d.tw.count}" + (" +x2" if d.x2 else ""))
+            f"taps {d.td.count}x{d.th.count}x{d.tw.count}" + (" +x2" if d.x2 else "") +
+            (" [" + _ROUTE_NAMES.get(wino_route(d)[0], "direct") + "]" if d.wino_ws else ""))
+
+
+_ROUTE_NAMES = {L.GG_ROUTE_FLAT8: "flat8", L.GG_ROUTE_W32P: "w32p", L.GG_ROUTE_BIG8: "big8", L.GG_ROUTE_SMALL: "small",
+                L.GG_ROUTE_FLAT22: "flat22", L.GG_ROUTE_REGION22: "region22"}
+
+
+def wino_route(d):
+    """(route, variant) of rehr_gather_gemm_wino_route: which fp32 Winograd kernel the library runs for this descriptor
+    when its scratch is attached (L.GG_ROUTE_*; 0 = none), and the kernel's variant."""
+    r = int(L.load().rehr_gather_gemm_wino_route(C.byref(d)))
+    return r & 255, (r >> 8) & 255
 
 
 def _gg_family(d):
-    """Profiling family of a launch: which kernel family the library picks for this descriptor."""
+    """Profiling family of a launch: the library says which kernel takes the descriptor (no guess from the tap counts).
+    The families stay the two transforms whose issue rates bench.py prices."""
+    if _prof is None:
+        return None             # no profile is running: _timed drops the family, so the library is not asked
     if not d.wino_ws:
         return "gather_gemm"
-    return "wino_conv" if d.th.count == 3 else "wino22_conv"
+    route = wino_route(d)[0]
+    if route == L.GG_ROUTE_NONE:
+        return "gather_gemm"
+    return "wino22_conv" if route in (L.GG_ROUTE_FLAT22, L.GG_ROUTE_REGION22) else "wino_conv"
 
 
 def gather_gemm(*args):

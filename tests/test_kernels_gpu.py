@@ -814,3 +814,101 @@ def test_winograd_wgrad_tap_colocation_is_bit_identical(monkeypatch):
     rw, rb = torch.autograd.grad(F.conv3d(xr, wr, br, 1, 1), [wr, br], dy.double().cpu())
     _close(out[True][0], rw)
     _close(out[True][1], rb)
+
+
+_FIRST_LAUNCH = """
+import json, sys
+sys.path.insert(0, {root!r})
+import torch
+import torch.nn.functional as F
+from rehrseg_amd import hip_backend, ops
+dev = torch.device("cuda:0")
+def mk(*shape, seed):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float32)
+def err(got, ref):
+    return float((got.double().cpu() - ref).abs().max() / ref.abs().max())
+res = {{}}
+with torch.no_grad():
+    # nnU-Net's 16^3 stage: the three depth taps as three parts of ONE big-tile grid (the split entry)
+    x, w = mk(2, 128, 16, 16, 16, seed=263), mk(128, 128, 3, 3, 3, seed=264) / (128 * 27) ** 0.5
+    b, ga, be = mk(128, seed=265), mk(128, seed=266), mk(128, seed=267)
+    y = ops.fused_conv3d(x.to(dev), w.to(dev), b.to(dev), 1, 1, inorm=(ga.to(dev), be.to(dev)), act=ops.ACT_LRELU, slope=0.01)
+    res["split_launches"] = hip_backend.wino_launches
+    ref = F.leaky_relu(F.instance_norm(F.conv3d(x.double(), w.double(), b.double(), 1, 1), weight=ga.double(),
+                                       bias=be.double()), 0.01)
+    res["split_err"] = err(y, ref)
+    # then the plain launch of the same kernel
+    x, w, b = mk(1, 64, 4, 16, 16, seed=268), mk(64, 64, 3, 3, 3, seed=269) / (64 * 27) ** 0.5, mk(64, seed=270)
+    y = ops.fused_conv3d(x.to(dev), w.to(dev), b.to(dev), 1, 1)
+    res["plain_launches"] = hip_backend.wino_launches - res["split_launches"]
+    res["plain_err"] = err(y, F.conv3d(x.double(), w.double(), b.double(), 1, 1))
+print("RESULT " + json.dumps(res))
+"""
+
+
+def test_first_winograd_launch_of_a_process_is_the_split_entry():
+    """The big-tile kernel needs its dynamic-LDS limit raised before its first launch, whichever entry launches it first:
+    in a fresh process the 3-part split of test_winograd_depth_tap_split_half_filled_grid comes first, then one plain
+    launch (1 x 64 x 4 x 16 x 16, 64 -> 64); both against fp64 at that test's tolerance."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _FIRST_LAUNCH.format(root=root)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    print(res)
+    assert res["split_launches"] == 3 and res["plain_launches"] == 1, res
+    assert res["split_err"] <= TOL and res["plain_err"] <= TOL, res
+
+
+ROUTED = [  # route, tolerance against the direct kernels, Cin, Cout, K, stride, pad, transposed, dims: the heads of the tables above
+    ("flat8", TOL, 128, 128, (3, 3, 3), 1, 1, False, (32, 4, 12, 12)),
+    ("flat8", TOL, 32, 128, (3, 3, 3), 1, 1, False, (7, 5, 24, 24)),
+    ("flat22", TOL, 128, 128, (3, 4, 4), (1, 2, 2), 1, True, (32, 8, 12, 12)),
+    ("flat22", TOL, 64, 128, (3, 4, 4), (1, 2, 2), 1, True, (12, 6, 24, 24)),
+    ("big8", 2e-5, 64, 64, (3, 3, 3), 1, 1, False, (1, 4, 16, 16)),
+    ("w32p", TOL, 32, 32, (3, 3, 3), 1, 1, False, (1, 4, 16, 16)),
+    ("region22", TOL, 64, 64, (3, 4, 4), (1, 2, 2), 1, True, (1, 3, 16, 16)),
+    ("small", TOL, 64, 96, (3, 3, 3), 1, 1, False, (1, 2, 8, 16)),
+    ("none", TOL, 64, 128, (1, 1, 1), (1, 2, 2), 0, False, (2, 3, 16, 14)),
+]
+
+
+@pytest.mark.parametrize("route,tol,Cin,Cout,K,stride,pad,transposed,dims", ROUTED)
+def test_route_query_names_the_kernel_that_runs(route, tol, Cin, Cout, K, stride, pad, transposed, dims, monkeypatch):
+    """The route query names the expected kernel for the descriptors of a real call, the call counts exactly those
+    descriptors in hip_backend.wino_launches, and the result equals the one with the Winograd kernels off -- 2e-5 for the
+    big tile as in test_winograd_big_tile_kernel_against_direct_kernel_and_fp64, else the 1e-4 the tests of those kernels
+    use.  (Python attaches a scratch where rehr_gather_gemm_wino_bytes is non-zero, so "route != 0 where a scratch was
+    attached" repeats on real descriptors what tests/test_wino_plan_cpu.py asserts on the table; the content here is the
+    kernel's name and the parity.)"""
+    from rehrseg_amd import hip_backend as hb
+    from rehrseg_amd import lib as L
+    N, D, H, W = dims
+    x = _mk(N, Cin, D, H, W, seed=300).to(_dev())
+    w = (_mk(*((Cin, Cout) if transposed else (Cout, Cin)), *K, seed=301) / (Cin * K[0] * K[1] * K[2]) ** 0.5).to(_dev())
+    b = _mk(Cout, seed=302).to(_dev())
+    seen, attach = [], hb._attach_ws
+
+    def spy(descs, n, needs, sigs, wp):
+        keep = attach(descs, n, needs, sigs, wp)
+        seen.append(([hb.wino_route(descs[i])[0] for i in range(n)], [bool(descs[i].wino_ws) for i in range(n)]))
+        return keep
+
+    out, launches = {}, {}
+    with torch.no_grad():
+        for flag in (True, False):
+            monkeypatch.setattr(hb, "USE_WINOGRAD", flag)
+            monkeypatch.setattr(hb, "_attach_ws", spy if flag else attach)
+            before = hb.wino_launches
+            out[flag] = ops.fused_conv3d(x, w, b, stride, pad, transposed=transposed)
+            launches[flag] = hb.wino_launches - before
+    assert seen
+    for routes, given in seen:
+        assert [r != L.GG_ROUTE_NONE for r in routes] == given, seen
+    assert launches == {True: sum(r != L.GG_ROUTE_NONE for routes, _ in seen for r in routes), False: 0}, (launches, seen)
+    want = getattr(L, "GG_ROUTE_" + route.upper())
+    assert want in {r for routes, _ in seen for r in routes}, seen
+    _close(out[True], out[False].double().cpu(), tol)

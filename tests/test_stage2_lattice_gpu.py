@@ -15,7 +15,7 @@ transposed convs, two-source convs and second convs, the 1x1x1 logits conv.  Sta
 stages 0-2 keep the full width and two 16-row region rows and are cut in H and D as far as the routing stays what it
 is at the full lattice: the Python-side picks (ops.choose_tile, the part count of ops._tap_split, ops.pad_rows) and a
 restatement of the library's acceptance rules (_wino_fwd, _halo_bf16, _wino_wgrad, _tconv_ks below; read from
-wino_workspace_bytes, plan_flat8, halo_conv_bf16_try, wino_wgrad's plan, tconv_ks_match) are asserted equal for the
+wino_region_plan, plan_flat8, halo_conv_bf16_try, wino_wgrad's plan, tconv_ks_match) are asserted equal for the
 two lattices, and test_reduced_lattice_takes_the_kernels_of_the_full_lattice runs the fp32 layer at the full lattice on
 the device and compares the Winograd launch counters.
 Tolerances are the neighbouring suites': fp32 1e-4 of the reference's max (test_kernels_gpu.py); bf16 without
@@ -182,8 +182,8 @@ def _up(a, b):
 
 
 def _wino_fwd(lat, Npad, N, kd):
-    """fp32, unit-stride 3x3 plane taps, kd <= 3 depth taps: the Winograd kernel the library picks (wino_flat8_conv_try's
-    plan_flat8, then wino_workspace_bytes / wino_conv_try), or None."""
+    """fp32, unit-stride 3x3 plane taps, kd <= 3 depth taps: the Winograd kernel the library picks (wino_route: wino_flat8_plan's
+    plan_flat8, then wino_region_plan), or None."""
     Ld, Lh, Lw = lat
     if Npad % 64 == 0 and Lh >= 6 and 6 <= Lw <= 64 and not (Lh % 16 == 0 and Lw % 16 == 0):
         nth, ntw = -(-Lh // 2), -(-Lw // 2)
