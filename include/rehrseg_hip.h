@@ -433,6 +433,7 @@ int rehr_uasr_mix_bwd_f32(const float* om, const float* ue, const float* wu, con
  * channel that Distiller's structure loss compares (CriterionPairWiseforWholeFeatAfterPool,
  * models/seg_model.py:95-113; MaxPool2d(ceil_mode=True) with even H, W).  x [slices][H][W][C] (NDHWC slices),
  * y [slices][2][2][C], idx = row-major position of the first maximum inside its slice (for the backward).
+ * A NaN in a window is its result (the last one, as in ATen's scan), and idx points at it.  Any C >= 1.
  * bwd: dx is zero-filled, then dx[slice][idx][c] = dy[slice][q][c].                                          */
 int rehr_quad_maxpool_fwd_f32(const float* x, float* y, int32_t* idx, int64_t slices,
                               int32_t H, int32_t W, int32_t C, void* stream);

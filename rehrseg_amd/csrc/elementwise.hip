@@ -399,7 +399,9 @@ __global__ void window_stem_assemble_kernel(const float* __restrict__ g0, const 
 // 64-channel feature map with a (H/2, W/2) window: 4 outputs per slice and channel.  ATen's NHWC pooling kernel
 // walks such a window serially per output (0.55 ms for 128 slices of 64x64); here a block owns one (slice,
 // quadrant): lanes = channels (coalesced voxel records), 4 row groups, one LDS step.  idx = row-major position
-// of the FIRST maximum inside the slice (what MaxPool2d's backward uses).
+// of the FIRST maximum inside the slice (what MaxPool2d's backward uses).  A NaN beats every number, and among
+// several NaNs of a window the LAST one is kept: ATen's serial scan replaces its maximum on `v > max || isnan(v)`.
+// Channels are walked from a block-uniform base (the loop holds barriers): any C >= 1 is safe.
 __global__ __launch_bounds__(256) void quad_maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                int* __restrict__ idx, int H, int W, int C) {
   __shared__ float sv[256];
@@ -409,10 +411,12 @@ __global__ __launch_bounds__(256) void quad_maxpool_fwd_kernel(const float* __re
   const int h0 = (qd >> 1) * ph, w0 = (qd & 1) * pw;
   const int lanes = C < 256 ? C : 256, groups = 256 / lanes;
   const int c_l = threadIdx.x % lanes, g = threadIdx.x / lanes;
-  for (int c = c_l; c < C; c += lanes) {
+  for (int cb = 0; cb < C; cb += lanes) {
+    const int c = cb + c_l;
+    const bool live = c < C;
     float best = -INFINITY;
     int bi = (h0 * W + w0);
-    if (g < groups) {
+    if (live && g < groups) {
       for (int r = g; r < ph; r += groups) {
         const float* row = x + (((int64_t)slice * H + h0 + r) * W + w0) * C + c;
         for (int q = 0; q < pw; ++q) {
@@ -424,11 +428,13 @@ __global__ __launch_bounds__(256) void quad_maxpool_fwd_kernel(const float* __re
     sv[threadIdx.x] = best;
     si[threadIdx.x] = bi;
     __syncthreads();
-    if (g == 0) {
+    if (live && g == 0) {
       for (int k = 1; k < groups; ++k) {
         const float v = sv[k * lanes + c_l];
         const int vi = si[k * lanes + c_l];
-        if (v > best || (v == best && vi < bi)) { best = v; bi = vi; }
+        const bool vn = v != v, bn = best != best;
+        // the groups interleave rows: numbers tie-break to the lower position, NaNs to the higher one
+        if (vn ? (!bn || vi > bi) : (!bn && (v > best || (v == best && vi < bi)))) { best = v; bi = vi; }
       }
       y[((int64_t)slice * 4 + qd) * C + c] = best;
       idx[((int64_t)slice * 4 + qd) * C + c] = bi;

@@ -670,7 +670,8 @@ def test_winograd_wgrad_64x64_block_against_direct_kernel_and_fp64():
     _close(out[True][1], rb)
 
 
-@pytest.mark.parametrize("K,D,N,hw", [(16, 4, 2, (24, 40)), (4, 3, 1, (7, 9)), (8, 8, 3, (5, 5)), (32, 2, 2, (33, 17))])
+@pytest.mark.parametrize("K,D,N,hw", [(16, 4, 2, (24, 40)), (4, 3, 1, (7, 9)), (8, 8, 3, (5, 5)), (32, 2, 2, (33, 17)),
+                                      (4, 3, 1, (420, 420))])   # 529 200 voxel-slices > 2048 blocks x 256: grid-stride
 def test_uasr_mix(K, D, N, hw):
     """rehr_uasr_mix_{fwd,bwd}_f32 against the reference's candidate loop in fp64 (oracle.flavr_oracle.uasr_head,
     FLAVR_arch.py:203-246): blended image / segmentation, uncertainty, and the gradients of both 1x1 responses and of
