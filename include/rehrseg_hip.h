@@ -152,6 +152,18 @@ int64_t rehr_gather_gemm_wino_bytes(const rehr_gather_gemm_desc* d);
 #define REHR_GG_ROUTE_FLAT22 5   /* F(2x2,2x2), flattened tiles */
 #define REHR_GG_ROUTE_REGION22 6 /* F(2x2,2x2), 16 x 16 regions */
 int rehr_gather_gemm_wino_route(const rehr_gather_gemm_desc* d);
+/* Which direct kernel a call of rehr_gather_gemm_multi_f32 (bf16 = 0) or rehr_gather_gemm_multi_bf16 (bf16 != 0) with
+ * these `count` descriptors runs for each part that no Winograd kernel takes: routes[i] = kind | variant << 8.
+ * HALO variants, in the order of preference -- fp32: 1 / 2 for the 64- / 32-channel tile; bf16: 1 / 2 / 3 for the
+ * bricks 4x8x16 / 8x8x8 / 2x16x16; else 0.  TCONV_KS: every part carries it (one launch runs them all).  NONE: no direct
+ * kernel reaches the operands, the call returns REHR_ENOSUP unless a Winograd kernel takes the part.
+ * Returns REHR_OK, or REHR_EINVAL exactly when the launch would (routes is then not written).  The same decision
+ * drives the launch.  Reads no operand memory. */
+#define REHR_GG_DIRECT_NONE 0
+#define REHR_GG_DIRECT_GENERIC 1   /* the per-tap gather kernels; the generic parts of a call share one grid */
+#define REHR_GG_DIRECT_HALO 2      /* input brick with its halo staged in LDS (halo_conv.hip, halo_conv_bf16.hip) */
+#define REHR_GG_DIRECT_TCONV_KS 3  /* kernel == stride transposed convolution, all stride phases in one block */
+int rehr_gather_gemm_direct_route(const rehr_gather_gemm_desc* descs, int32_t count, int32_t bf16, int32_t* routes);
 int rehr_gather_gemm_f32(const rehr_gather_gemm_desc* d, void* stream);
 /* The stride phases of ONE layer (same x1/x2, wp, y, N, Npad; count <= 8), differing
  * only in lattice, taps and destination offset, in a single grid.                   */

@@ -23,7 +23,7 @@
 //    sum-of-squares that SEGating's pool and InstanceNorm3d need (double
 //    atomics, one per channel per wave).
 #include "common.h"
-#include "halo_conv.h"
+#include "halo_shared.h"
 #include "wino_shared.h"
 
 namespace {
@@ -404,26 +404,19 @@ static int wino_run(WinoRoute r, const rehr_gather_gemm_desc* ds, int count, con
 }
 
 extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, int32_t count, void* stream) {
-  if (descs == nullptr || count < 1 || count > MAX_PHASES) return REHR_EINVAL;
-  for (int i = 0; i < count; ++i) {
-    const int rc = validate(descs[i]);
-    if (rc != REHR_OK) return rc;
-    // phases of one layer: same operands and channel geometry
-    if (descs[i].Npad != descs[0].Npad || descs[i].N != descs[0].N || descs[i].wp != descs[0].wp ||
-        descs[i].x1 != descs[0].x1)
-      return REHR_EINVAL;  // (y may differ: split-K partials go to separate slabs)
-    // (Cin and c1 may differ as well, unlike in rehr_gather_gemm_multi_bf16: the K step is 32 channels for every phase)
-  }
+  // the direct kernel of every part (halo_shared.h: every part validated first); what a Winograd kernel takes below
+  // does not use its route
+  DirectRoute route[MAX_PHASES];
+  const int rrc = direct_route(descs, count, 4, route);
+  if (rrc != REHR_OK) return rrc;
   hipStream_t st = (hipStream_t)stream;
   // REHR_GG_WS_ONLY: the weight transforms of this call and nothing else (wino_run; whatever no Winograd kernel takes
   // has nothing to prepare)
   const bool ws_only = (descs[0].flags & REHR_GG_WS_ONLY) != 0;
   for (int i = 1; i < count; ++i)
     if ((descs[i].flags ^ descs[0].flags) & (REHR_GG_WS_ONLY | REHR_GG_WS_READY)) return REHR_EINVAL;
-  if (count > 1 && !ws_only) {   // the stride phases of a kernel == stride transposed convolution: one fused launch
-    const int trc = tconv_ks_try(descs, count, false, st);
-    if (trc != REHR_ENOSUP) return trc;
-  }
+  // the stride phases of a kernel == stride transposed convolution: one fused launch
+  if (route[0].kind == DIRECT_TCONV_KS && !ws_only) return tconv_ks_launch(descs, count, false, st);
   WinoPlan plan{};
   if (count > 1 && descs[0].wino_ws != nullptr) {
     // All parts in one Winograd grid, or none.  Tap-range parts of a split-K launch (many depth taps; or the single
@@ -452,14 +445,14 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
       }
     }
     if (ws_only) continue;
-    if (descs[i].tile_d >= 0) {  // the halo-tile kernel takes what it is good at, one launch each
-      const int hrc = halo_conv_try(descs[i], st);
-      if (hrc == REHR_OK) continue;
-      if (hrc != REHR_ENOSUP) return hrc;
+    if (route[i].kind == DIRECT_HALO) {  // the halo-tile kernel takes what it is good at, one launch each
+      const int hrc = halo_f32_launch(route[i].halo, st);
+      if (hrc != REHR_OK) return hrc;
+    } else if (route[i].kind == DIRECT_GENERIC) {
+      pm.ph[n++] = route[i].gg;
+    } else {
+      return REHR_ENOSUP;
     }
-    const int rc = gg_plan(descs[i], pm.ph[n], 4, BK);
-    if (rc != REHR_OK) return rc;
-    ++n;
   }
   if (n == 0) return REHR_OK;
   return launch_generic(pm, n, st);
@@ -476,6 +469,16 @@ extern "C" int rehr_gather_gemm_wino_route(const rehr_gather_gemm_desc* dp) {
   if (dp == nullptr || validate(*dp) != REHR_OK) return REHR_GG_ROUTE_NONE;
   const WinoRoute r = wino_route(*dp, plan);
   return r == WINO_NONE ? REHR_GG_ROUTE_NONE : (int)r | (plan.variant << 8);
+}
+
+extern "C" int rehr_gather_gemm_direct_route(const rehr_gather_gemm_desc* descs, int32_t count, int32_t bf16,
+                                             int32_t* routes) {
+  DirectRoute route[MAX_PHASES];
+  if (routes == nullptr) return REHR_EINVAL;
+  const int rc = direct_route(descs, count, bf16 ? 2 : 4, route);
+  if (rc != REHR_OK) return rc;
+  for (int i = 0; i < count; ++i) routes[i] = route[i].kind | (route[i].variant << 8);
+  return REHR_OK;
 }
 
 extern "C" int rehr_gather_gemm_f32(const rehr_gather_gemm_desc* dp, void* stream) {

@@ -18,9 +18,7 @@
 //  * register-staged pipeline two K steps ahead, branch-free raw buffer loads (out-of-range = zero padding), as
 //    in the fp32 kernel.
 #include "common.h"
-#include "gg_shared.h"
-
-int halo_conv_bf16_try(const rehr_gather_gemm_desc& d, hipStream_t stream);  // halo_conv_bf16.hip
+#include "halo_shared.h"
 
 namespace {
 
@@ -340,14 +338,9 @@ int launch_gb(const GGMulti& pm, int count, hipStream_t stream) {
                    gather_gemm_bf16_multi_kernel<BM, BN, WGM, WGN, LDSBUF, BK>, NTHREADS, smem>(pm, count, stream);
 }
 
-int validate(const rehr_gather_gemm_desc& d) { return gg_validate(d, ES); }
-
-// 64-channel K steps when neither Cin nor the concat split leaves a half chunk
-bool chunk64(const rehr_gather_gemm_desc& d) { return d.Cin % 64 == 0 && (d.c1 == d.Cin || d.c1 % 64 == 0); }
-
 int launch_generic(const GGMulti& pm, int count, hipStream_t st) {
   const int npad = pm.ph[0].d.Npad;
-  const bool k64 = chunk64(pm.ph[0].d);
+  const bool k64 = gg_chunk64(pm.ph[0].d);
   if (npad % 128 == 0)
     return k64 ? launch_gb<128, 128, 2, 2, 2, 64>(pm, count, st) : launch_gb<128, 128, 2, 2, 2, 32>(pm, count, st);
   if (npad % 64 == 0)
@@ -372,41 +365,30 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ in, __bf16* _
 
 }  // namespace
 
+// route (halo_shared.h: every part validated, one decision per part), then execute
 extern "C" int rehr_gather_gemm_multi_bf16(const rehr_gather_gemm_desc* descs, int32_t count, void* stream) {
-  if (descs == nullptr || count < 1 || count > MAX_PHASES) return REHR_EINVAL;
-  if (count > 1) {   // the stride phases of a kernel == stride transposed convolution: one fused launch (tconv_ks.hip)
-    bool ok = true;
-    for (int i = 0; i < count && ok; ++i) ok = validate(descs[i]) == REHR_OK;
-    if (ok) {
-      const int trc = tconv_ks_try(descs, count, true, (hipStream_t)stream);
-      if (trc != REHR_ENOSUP) return trc;
-    }
-  }
+  DirectRoute route[MAX_PHASES];
+  const int rrc = direct_route(descs, count, ES, route);
+  if (rrc != REHR_OK) return rrc;
+  hipStream_t st = (hipStream_t)stream;
+  if (route[0].kind == DIRECT_TCONV_KS) return tconv_ks_launch(descs, count, true, st);
   GGMulti pm;
   pm.interleave = 0;
   pm.count = 0;
   pm.no_interleave = (descs[0].debug_flags & REHR_DBG_GG_INTERLEAVE) ? 0 : 1;
   int n = 0;
   for (int i = 0; i < count; ++i) {
-    int rc = validate(descs[i]);
-    if (rc != REHR_OK) return rc;
-    if (descs[i].Npad != descs[0].Npad || descs[i].N != descs[0].N || descs[i].wp != descs[0].wp ||
-        descs[i].x1 != descs[0].x1 || descs[i].Cin != descs[0].Cin || descs[i].c1 != descs[0].c1)
-      return REHR_EINVAL;   // (Cin, c1: stricter than rehr_gather_gemm_multi_f32 -- launch_generic takes chunk64() from phase 0)
-    // (tap-range parts of a split-K launch -- they differ in y -- stay together in ONE generic grid: a halo launch per
-    // part would run them one after the other on a few CUs each)
-    const bool split_part = count > 1 && descs[i].y != descs[(i + 1) % count].y;
-    if (!(descs[i].debug_flags & REHR_DBG_GG_NO_HALO) && !split_part) {   // unit-stride 3x3(x3) taps: input brick + halo staged in LDS
-      rc = halo_conv_bf16_try(descs[i], (hipStream_t)stream);
-      if (rc == REHR_OK) continue;
-      if (rc != REHR_ENOSUP) return rc;
+    if (route[i].kind == DIRECT_HALO) {   // one launch each, now; the generic phases share one grid at the end
+      const int rc = halo_bf16_launch(route[i].halo, st);
+      if (rc != REHR_OK) return rc;
+    } else if (route[i].kind == DIRECT_GENERIC) {
+      pm.ph[n++] = route[i].gg;
+    } else {
+      return REHR_ENOSUP;
     }
-    rc = gg_plan(descs[i], pm.ph[n], ES, chunk64(descs[i]) ? 64 : 32);
-    if (rc != REHR_OK) return rc;
-    ++n;
   }
   if (n == 0) return REHR_OK;
-  return launch_generic(pm, n, (hipStream_t)stream);
+  return launch_generic(pm, n, st);
 }
 
 extern "C" int rehr_gather_gemm_bf16(const rehr_gather_gemm_desc* dp, void* stream) {

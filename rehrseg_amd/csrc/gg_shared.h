@@ -101,6 +101,9 @@ inline int gg_plan(const rehr_gather_gemm_desc& d, GGParams& p, int es, int bk) 
   return REHR_OK;
 }
 
+// bf16: 64-channel K steps when neither Cin nor the concat split leaves a half chunk (else 32, as in fp32)
+inline bool gg_chunk64(const rehr_gather_gemm_desc& d) { return d.Cin % 64 == 0 && (d.c1 == d.Cin || d.c1 % 64 == 0); }
+
 // ---- launch of `count` planned phases: the single-launch kernel for one, one shared grid for several ----
 // (the dynamic-LDS attribute is set once per instantiation, i.e. once per kernel pair)
 template <void (*KERN1)(GGParams), void (*KERNM)(GGMulti), int NT, size_t SMEM>
@@ -135,7 +138,3 @@ int gg_launch(const GGMulti& pm, int count, hipStream_t stream) {
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }
-
-// kernel == stride transposed convolution, fp32 and bf16: all stride phases of a 128-voxel input tile in one block
-// (tconv_ks.hip).  REHR_ENOSUP: not a shape for it.
-int tconv_ks_try(const rehr_gather_gemm_desc* ds, int count, bool bf16, hipStream_t stream);

@@ -11,25 +11,13 @@
 // range of tiles and fetch the next (tile, chunk) halo into registers during the current
 // sweep, so HBM/L2 latency hides behind ~28k-55k cycles of MFMA work.
 #include "common.h"
-#include "gg_shared.h"
-#include "halo_conv.h"
+#include "halo_shared.h"
 
 namespace {
 
 constexpr int BD = 2, BH = 8, BW = 8, BVOX = BD * BH * BW;  // lattice brick = 128 rows
 constexpr int LDX = 36;                                     // LDS row stride (32 + 4)
 constexpr int MAXX = 13;                                    // halo rows staged per thread (32 rows per pass)
-
-struct HaloParams {
-  rehr_gather_gemm_desc d;
-  int HD, HH, HW, hvox;
-  int mind, minh, minw;
-  int nb_d, nb_h, nb_w, tiles_per_img;
-  int64_t ntiles;       // N * tiles_per_img
-  int tiles_per_block;
-  int kchunks;
-  uint32_t wp_bytes;
-};
 
 // WGM x WGN waves; wave tile (BVOX / WGM) x (BN / WGN)
 template <int BN, int WGM, int WGN>
@@ -252,61 +240,30 @@ __global__ __launch_bounds__(256, 2) void halo_conv_kernel(const HaloParams p) {
   }
 }
 
-template <int BN, int WGM, int WGN>
-int launch(const HaloParams& p, size_t smem, hipStream_t stream) {
-  auto kern = halo_conv_kernel<BN, WGM, WGN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            96 * 1024) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
-  const int64_t blocks_x = (p.ntiles + p.tiles_per_block - 1) / p.tiles_per_block;
-  dim3 grid((unsigned)blocks_x, p.d.Npad / BN, 1);
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, p);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+
+// The variants in the order of preference: output-channel tile 64 (2 x 2 waves) when Npad is a multiple of 64, else 32
+// (4 x 1 waves).  A block holds MAXX * 32 = 416 halo rows in registers on their way to LDS; launches stay at or below
+// 80 KB of the 96 KB attribute, so that two blocks share a CU.  1024 persistent blocks over the output-channel tiles:
+// two rounds of the 512 that are resident (256 CUs x 2), and a block walks >= 2 tiles when there are that many.
+constexpr HaloBrickSpec spec(int bn) {
+  return {BD, BH, BW, bn, 256, /*min_ld*/ BD, /*es*/ 4, /*max_hvox*/ MAXX * 32, /*max_grow*/ -1, /*lds_rows*/ 0,
+          /*lds_row*/ LDX * (int)sizeof(float), /*lds_fixed*/ BVOX * (int)sizeof(int), /*lds_max*/ 80 * 1024,
+          /*lds_attr*/ 96 * 1024, /*want_blocks*/ 1024, /*max_y_bytes*/ 0, /*max_ntiles*/ 0};
 }
+constexpr HaloBrickSpec SPEC[] = {spec(64), spec(32)};
 
 }  // namespace
 
-// REHR_ENOSUP = "not this kernel's case" (the caller then uses the generic gather-GEMM).
-int halo_conv_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  if (d.sd != 1 || d.sh != 1 || d.sw != 1) return REHR_ENOSUP;
-  if (d.Npad > 64) return REHR_ENOSUP;
+bool halo_f32_plan(const rehr_gather_gemm_desc& d, HaloPlan& plan) {
+  if (d.sd != 1 || d.sh != 1 || d.sw != 1) return false;
+  if (d.Npad > 64) return false;
   const int T = d.td.count * d.th.count * d.tw.count;
-  if (T < 9 || T > 64) return REHR_ENOSUP;   // few taps: the gather kernel is already cheap per byte
-  if (d.Ld < BD || d.Lh < BH || d.Lw < BW) return REHR_ENOSUP;
-  const int64_t nb_d = (d.Ld + BD - 1) / BD, nb_h = (d.Lh + BH - 1) / BH, nb_w = (d.Lw + BW - 1) / BW;
-  if (nb_d * BD * nb_h * BH * nb_w * BW * 10 > (int64_t)d.Ld * d.Lh * d.Lw * 13) return REHR_ENOSUP;
-  int mn[3], mx[3];
-  span(d.td, d.bd, &mn[0], &mx[0]);
-  span(d.th, d.bh, &mn[1], &mx[1]);
-  span(d.tw, d.bw, &mn[2], &mx[2]);
-  HaloParams p;
-  p.d = d;
-  p.HD = BD + mx[0] - mn[0]; p.HH = BH + mx[1] - mn[1]; p.HW = BW + mx[2] - mn[2];
-  p.hvox = p.HD * p.HH * p.HW;
-  if (p.hvox > MAXX * 32 || p.HH > 1023 || p.HW > 1023) return REHR_ENOSUP;
-  const size_t smem = (size_t)p.hvox * LDX * sizeof(float) + BVOX * sizeof(int);
-  if (smem > 80 * 1024) return REHR_ENOSUP;
-  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 4)) return REHR_ENOSUP;
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return REHR_ENOSUP;
-  p.mind = mn[0]; p.minh = mn[1]; p.minw = mn[2];
-  p.nb_d = (int)nb_d; p.nb_h = (int)nb_h; p.nb_w = (int)nb_w;
-  p.tiles_per_img = (int)(nb_d * nb_h * nb_w);
-  p.ntiles = (int64_t)d.N * p.tiles_per_img;
-  p.kchunks = (d.Cin + 31) / 32;
-  const int64_t wb = gg_wp_bytes(d, 4);
-  if (wb >= GG_BUF_LIMIT) return REHR_ENOSUP;
-  p.wp_bytes = (uint32_t)wb;
-  // persistent blocks: 512 resident (256 CUs x 2); full rounds, >= 2 tiles each when possible
-  const int n_tiles = d.Npad / (d.Npad % 64 == 0 ? 64 : 32);
-  int64_t want = 1024 / n_tiles;
-  if (want > p.ntiles) want = p.ntiles;
-  if (want < 1) want = 1;
-  p.tiles_per_block = (int)((p.ntiles + want - 1) / want);
-  if (d.Npad % 64 == 0) return launch<64, 2, 2>(p, smem, stream);
-  return launch<32, 4, 1>(p, smem, stream);
+  if (T < 9 || T > 64) return false;   // few taps: the gather kernel is already cheap per byte
+  plan.variant = d.Npad % 64 == 0 ? 1 : 2;
+  return halo_brick_plan(d, SPEC[plan.variant - 1], plan.p, plan.smem);
+}
+
+int halo_f32_launch(const HaloPlan& plan, hipStream_t stream) {
+  if (plan.variant == 1) return halo_launch<halo_conv_kernel<64, 2, 2>>(plan, SPEC[0], stream);
+  return halo_launch<halo_conv_kernel<32, 4, 1>>(plan, SPEC[1], stream);
 }

@@ -23,7 +23,7 @@
 // Epilogue semantics as in the gather kernel: bias, ReLU / LeakyReLU, bf16 (or fp32) store, fp64 statistics formed
 // from the fp32 values.
 #include "common.h"
-#include "gg_shared.h"
+#include "halo_shared.h"
 
 namespace {
 
@@ -43,20 +43,9 @@ template <int NWV> struct HBW {
 constexpr int BVOX = 512;
 constexpr int BN = 32;
 
-struct HBParams {
-  rehr_gather_gemm_desc d;
-  int HD, HH, HW, hvox;
-  int mind, minh, minw;
-  int nb_d, nb_h, nb_w, tiles_per_img;
-  int64_t ntiles;
-  int tiles_per_block;
-  int kchunks;
-  uint32_t wp_bytes;
-};
-
 // NT3 = taps / 3 (9: 3x3x3, 3: 1x3x3): the sweep is fully unrolled so that the next halo's loads can be spread over it
 template <int BD, int BH, int BW, int NT3, int NWV>
-__global__ __launch_bounds__(64 * NWV, 1) void halo_conv_bf16_kernel(const HBParams p) {
+__global__ __launch_bounds__(64 * NWV, 1) void halo_conv_bf16_kernel(const HaloParams p) {
   static_assert(BD * BH * BW == BVOX, "512 voxels");
   constexpr int NTHR = HBW<NWV>::NTHR, RPP = HBW<NWV>::RPP, FM = HBW<NWV>::FM;
   constexpr int MAXX = ((BD + 2) * (BH + 2) * (BW + 2) + RPP - 1) / RPP;
@@ -452,80 +441,49 @@ __global__ __launch_bounds__(64 * NWV, 1) void halo_conv_bf16_kernel(const HBPar
   if (want_stats && stats_n >= 0) flush_stats(stats_n);
 }
 
-template <int BD, int BH, int BW, int NT3, int NWV>
-int launch(HBParams p, hipStream_t stream) {
+constexpr int NWV = 8;   // eight waves per block, two per SIMD; the four-wave organisation of round 2's first half was
+                         // 1.0 ms per step slower on the bf16 cfg-3 step: profiles/r03_ab_superseded.txt
+
+// One variant: a 512-voxel brick, at 27 or 9 taps (the sweep is unrolled per tap count).  Depth may fall short of the
+// brick down to its half; the halo is at most one voxel per side (the LDS rows below are sized for brick + 2); the LDS
+// holds the staged rows, the weights of all taps of a chunk and the rows' output offsets, below 158 KB: one block per
+// CU, hence 256 persistent blocks over the output-channel tiles.  y is stored through one buffer.
+constexpr HaloBrickSpec spec(int bd, int bh, int bw, int ntaps) {
   constexpr int RPP = HBW<NWV>::RPP;
-  const rehr_gather_gemm_desc& d = p.d;
-  if (d.Ld < (BD + 1) / 2 || d.Lh < BH || d.Lw < BW) return REHR_ENOSUP;
-  const int64_t nb_d = (d.Ld + BD - 1) / BD, nb_h = (d.Lh + BH - 1) / BH, nb_w = (d.Lw + BW - 1) / BW;
-  if (nb_d * BD * nb_h * BH * nb_w * BW * 10 > (int64_t)d.Ld * d.Lh * d.Lw * 13) return REHR_ENOSUP;  // <= 1.3x padding
-  p.HD = BD + p.HD; p.HH = BH + p.HH; p.HW = BW + p.HW;      // (the tap spans were left in HD/HH/HW)
-  p.hvox = p.HD * p.HH * p.HW;
-  if (p.HD > BD + 2 || p.HH > BH + 2 || p.HW > BW + 2) return REHR_ENOSUP;
-  constexpr int ntaps = 3 * NT3;
-  constexpr int XROWS = (((BD + 2) * (BH + 2) * (BW + 2) + RPP - 1) / RPP) * RPP;   // = MAXX * RPP in the kernel
-  const size_t smem = (size_t)XROWS * XROW + (size_t)ntaps * BN * WROW + (size_t)BVOX * sizeof(int);
-  if (smem > 158 * 1024) return REHR_ENOSUP;
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy * d.ldy * 2 >= (1ll << 32) - 64) return REHR_ENOSUP;   // buffer-addressed stores
-  p.nb_d = (int)nb_d; p.nb_h = (int)nb_h; p.nb_w = (int)nb_w;
-  p.tiles_per_img = (int)(nb_d * nb_h * nb_w);
-  p.ntiles = (int64_t)d.N * p.tiles_per_img;
-  if (p.ntiles >= (1ll << 31) - 4096) return REHR_ENOSUP;
-  // persistent blocks, one per CU: whole rounds of 256
-  const int n_tiles = d.Npad / BN;
-  int64_t want = 256 / n_tiles;
-  if (want < 1) want = 1;
-  if (want > p.ntiles) want = p.ntiles;
-  p.tiles_per_block = (int)((p.ntiles + want - 1) / want);
-  auto kern = halo_conv_bf16_kernel<BD, BH, BW, NT3, NWV>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            158 * 1024) != hipSuccess)
-      return REHR_EHIP;
-    attr_set = true;
-  }
-  const int64_t blocks_x = (p.ntiles + p.tiles_per_block - 1) / p.tiles_per_block;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks_x, n_tiles, 1), dim3(64 * NWV), smem, stream, p);
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
+  return {bd, bh, bw, BN, HBW<NWV>::NTHR, /*min_ld*/ (bd + 1) / 2, /*es*/ 2, /*max_hvox*/ 0, /*max_grow*/ 2,
+          /*lds_rows = MAXX * RPP in the kernel*/ ((bd + 2) * (bh + 2) * (bw + 2) + RPP - 1) / RPP * RPP,
+          /*lds_row*/ XROW, /*lds_fixed*/ ntaps * BN * WROW + BVOX * (int)sizeof(int), /*lds_max*/ 158 * 1024,
+          /*lds_attr*/ 158 * 1024, /*want_blocks*/ 256, /*max_y_bytes*/ (1ll << 32) - 64,
+          /*max_ntiles*/ (1ll << 31) - 4096};
 }
+// in the order of preference; [variant - 1][27 taps, 9 taps].  2 x 16 x 16 exists for 9 taps only.
+constexpr HaloBrickSpec SPEC[3][2] = {{spec(4, 8, 16, 27), spec(4, 8, 16, 9)},
+                                      {spec(8, 8, 8, 27), spec(8, 8, 8, 9)},
+                                      {spec(2, 16, 16, 27), spec(2, 16, 16, 9)}};
 
 }  // namespace
 
-// REHR_OK = launched; REHR_ENOSUP = not this kernel's case (the caller uses gather_gemm_bf16); other = error.
-int halo_conv_bf16_try(const rehr_gather_gemm_desc& d, hipStream_t stream) {
-  if (d.sd != 1 || d.sh != 1 || d.sw != 1) return REHR_ENOSUP;
+bool halo_bf16_plan(const rehr_gather_gemm_desc& d, HaloPlan& plan) {
+  if (d.sd != 1 || d.sh != 1 || d.sw != 1) return false;
   const int T = d.td.count * d.th.count * d.tw.count;
-  if (T != 27 && T != 9) return REHR_ENOSUP;   // 3x3x3 and 1x3x3 / 3x3x1 taps (the sweep is unrolled per tap count)
-  if (d.td.count > 3 || d.th.count > 3 || d.tw.count > 3) return REHR_ENOSUP;
-  if (d.c1 < d.Cin && d.c1 % BK) return REHR_ENOSUP;
-  if (d.Cout % 8 || d.ldy % 8 || ((uintptr_t)d.y & 15)) return REHR_ENOSUP;   // 16-byte pieces of a voxel's row
-  int mn[3], mx[3];
-  span(d.td, d.bd, &mn[0], &mx[0]);
-  span(d.th, d.bh, &mn[1], &mx[1]);
-  span(d.tw, d.bw, &mn[2], &mx[2]);
-  HBParams p;
-  p.d = d;
-  p.HD = mx[0] - mn[0]; p.HH = mx[1] - mn[1]; p.HW = mx[2] - mn[2];   // halo extents, completed per brick in launch()
-  p.mind = mn[0]; p.minh = mn[1]; p.minw = mn[2];
-  if (!gg_src_fits(d, (int64_t)d.Di * d.Hi * d.Wi, 2)) return REHR_ENOSUP;
-  if ((int64_t)d.N * d.Dy * d.Hy * d.Wy >= (1ll << 31)) return REHR_ENOSUP;
-  p.kchunks = (d.Cin + BK - 1) / BK;
-  const int64_t wb = gg_wp_bytes(d, 2);
-  if (wb >= GG_BUF_LIMIT) return REHR_ENOSUP;
-  p.wp_bytes = (uint32_t)wb;
-  // brick shapes in order of preference; one that pads the lattice by more than 1.3x (or does not fit it) declines
-  // (eight waves per block, two per SIMD; the four-wave organisation of round 2's first half was 1.0 ms per step slower
-  // on the bf16 cfg-3 step: profiles/r03_ab_superseded.txt)
-  int rc;
-  if (T == 27) {
-    rc = launch<4, 8, 16, 9, 8>(p, stream);
-    if (rc == REHR_ENOSUP) rc = launch<8, 8, 8, 9, 8>(p, stream);
-  } else {
-    rc = launch<4, 8, 16, 3, 8>(p, stream);
-    if (rc == REHR_ENOSUP) rc = launch<8, 8, 8, 3, 8>(p, stream);
-    if (rc == REHR_ENOSUP) rc = launch<2, 16, 16, 3, 8>(p, stream);
+  if (T != 27 && T != 9) return false;   // 3x3x3 and 1x3x3 / 3x3x1 taps
+  if (d.td.count > 3 || d.th.count > 3 || d.tw.count > 3) return false;
+  if (d.Cout % 8 || d.ldy % 8 || ((uintptr_t)d.y & 15)) return false;   // 16-byte pieces of a voxel's row
+  for (plan.variant = 1; plan.variant <= (T == 9 ? 3 : 2); ++plan.variant)
+    if (halo_brick_plan(d, SPEC[plan.variant - 1][T == 9], plan.p, plan.smem)) return true;
+  return false;
+}
+
+int halo_bf16_launch(const HaloPlan& plan, hipStream_t stream) {
+  const rehr_gather_gemm_desc& d = plan.p.d;
+  const bool nine = d.td.count * d.th.count * d.tw.count == 9;
+  const HaloBrickSpec& s = SPEC[plan.variant - 1][nine];
+  switch (plan.variant * 2 + nine) {
+    case 2: return halo_launch<halo_conv_bf16_kernel<4, 8, 16, 9, NWV>>(plan, s, stream);
+    case 3: return halo_launch<halo_conv_bf16_kernel<4, 8, 16, 3, NWV>>(plan, s, stream);
+    case 4: return halo_launch<halo_conv_bf16_kernel<8, 8, 8, 9, NWV>>(plan, s, stream);
+    case 5: return halo_launch<halo_conv_bf16_kernel<8, 8, 8, 3, NWV>>(plan, s, stream);
+    case 7: return halo_launch<halo_conv_bf16_kernel<2, 16, 16, 3, NWV>>(plan, s, stream);
+    default: return REHR_EINVAL;
   }
-  return rc;
 }

@@ -13,6 +13,7 @@
 // the 128 x C_out result is stored as full 128-byte lines (lanes = consecutive output channels).
 // HBM traffic = x once + y once (+ the weights from L2); a block does `phases` times the work per launch overhead.
 #include "common.h"
+#include "halo_shared.h"
 
 namespace {
 
@@ -262,9 +263,12 @@ __global__ __launch_bounds__(TK_THREADS, 2) void tconv_ks_bf16_kernel(const Tcon
 // against 345 / 119 us for the kernels above and 450 / 292 us for the generic grid, tools/bench_tconv_ks.py.)
 
 // The `count` descriptors are the stride phases of ONE kernel == stride transposed convolution
+// (true: tconv_launch launches them)
 bool tconv_ks_match(const rehr_gather_gemm_desc* ds, int count, bool bf16, TconvKsParams& p) {
   if (count < 2 || count > TK_MAXPH) return false;
   const rehr_gather_gemm_desc& d0 = ds[0];
+  if (d0.debug_flags & REHR_DBG_GG_NO_TCONV_KS) return false;
+  if (!bf16 && d0.Cin > 64) return false;   // fp32, 128 input channels: one block per CU (LDS) -- the generic grid is faster
   if (d0.x2 != nullptr || d0.c1 != d0.Cin || d0.Cin % TK_BK || d0.Cin > 128 || d0.Npad % 32 || d0.Npad > 128) return false;
   if (d0.act != REHR_ACT_NONE || d0.stats_mode != 0 || (d0.flags & REHR_GG_Y_F32)) return false;
   if (d0.osd * d0.osh * d0.osw != count) return false;
@@ -290,8 +294,7 @@ bool tconv_ks_match(const rehr_gather_gemm_desc* ds, int count, bool bf16, Tconv
     p.tap[i] = (d.td.k0 * d.KH + d.th.k0) * d.KW + d.tw.k0;
     p.yoff[i] = (d.obd * d.Hy + d.obh) * d.Wy + d.obw;
   }
-  const int align = bf16 ? 15 : 15;
-  if (((uintptr_t)d0.x1 | (uintptr_t)d0.wp) & align) return false;
+  if (((uintptr_t)d0.x1 | (uintptr_t)d0.wp) & 15) return false;
   if (bf16 ? (d0.ldx1 % 8 || d0.ldy % 2) : (d0.ldx1 % 4)) return false;
   p.x = d0.x1; p.wp = d0.wp; p.bias = d0.bias; p.y = d0.y;
   p.ldx = d0.ldx1; p.ldy = d0.ldy; p.Cin = d0.Cin; p.Cout = d0.Cout; p.Npad = d0.Npad;
@@ -299,54 +302,49 @@ bool tconv_ks_match(const rehr_gather_gemm_desc* ds, int count, bool bf16, Tconv
   p.sd = d0.osd; p.sh = d0.osh; p.sw = d0.osw;
   p.nph = count;
   p.vox_total = (int64_t)d0.N * d0.Di * d0.Hi * d0.Wi;
+  if ((p.vox_total + TK_BM - 1) / TK_BM >= (1ll << 31)) return false;   // one block per 128 input voxels
   p.lda = bf16 ? d0.Cin + 8 : d0.Cin + 4;
   return true;
 }
 
+// "set the dynamic-LDS attribute once, then launch", once per kernel instantiation
+template <void (*KERN)(TconvKsParams), int LDS_ATTR>
+int tconv_launch_kernel(const TconvKsParams& p, size_t smem, hipStream_t stream) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ATTR) != hipSuccess)
+      return REHR_EHIP;
+    attr = true;
+  }
+  const int64_t blocks = (p.vox_total + TK_BM - 1) / TK_BM;
+  hipLaunchKernelGGL(KERN, dim3((unsigned)blocks), dim3(TK_THREADS), smem, stream, p);
+  REHR_LAUNCH_CHECK();
+  return REHR_OK;
+}
+
 template <int NT>
 int tconv_launch(const TconvKsParams& p, bool bf16, hipStream_t stream) {
-  const int64_t blocks = (p.vox_total + TK_BM - 1) / TK_BM;
-  if (blocks >= (1ll << 31)) return REHR_ENOSUP;
-  if (!bf16 && p.Cin > 64) return REHR_ENOSUP;   // fp32, 128 input channels: one block per CU (LDS) -- the generic grid is faster
-  if (bf16) {
-    const size_t smem = ((size_t)TK_BM * p.lda + 2 * NT * 32 * TK_LDH) * 2 + TK_BM * sizeof(int);
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)tconv_ks_bf16_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) !=
-          hipSuccess)
-        return REHR_EHIP;
-      attr = true;
-    }
-    hipLaunchKernelGGL(tconv_ks_bf16_kernel<NT>, dim3((unsigned)blocks), dim3(TK_THREADS), smem, stream, p);
-  } else {
-    const size_t smem = ((size_t)TK_BM * p.lda + 2 * NT * 32 * TK_LD) * sizeof(float) + TK_BM * sizeof(int);
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)tconv_ks_f32_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) !=
-          hipSuccess)
-        return REHR_EHIP;
-      attr = true;
-    }
-    hipLaunchKernelGGL(tconv_ks_f32_kernel<NT>, dim3((unsigned)blocks), dim3(TK_THREADS), smem, stream, p);
-  }
-  return REHR_OK;
+  if (bf16)
+    return tconv_launch_kernel<tconv_ks_bf16_kernel<NT>, 72 * 1024>(
+        p, ((size_t)TK_BM * p.lda + 2 * NT * 32 * TK_LDH) * 2 + TK_BM * sizeof(int), stream);
+  return tconv_launch_kernel<tconv_ks_f32_kernel<NT>, 112 * 1024>(
+      p, ((size_t)TK_BM * p.lda + 2 * NT * 32 * TK_LD) * sizeof(float) + TK_BM * sizeof(int), stream);
 }
 
 }  // namespace
 
-// REHR_OK launched; REHR_ENOSUP: not the phases of a kernel == stride transposed convolution this kernel takes
-int tconv_ks_try(const rehr_gather_gemm_desc* ds, int count, bool bf16, hipStream_t stream) {
-  if (ds[0].debug_flags & REHR_DBG_GG_NO_TCONV_KS) return REHR_ENOSUP;
+bool tconv_ks_takes(const rehr_gather_gemm_desc* ds, int count, bool bf16) {
   TconvKsParams p;
-  if (!tconv_ks_match(ds, count, bf16, p)) return REHR_ENOSUP;
-  int rc;
+  return tconv_ks_match(ds, count, bf16, p);
+}
+
+int tconv_ks_launch(const rehr_gather_gemm_desc* ds, int count, bool bf16, hipStream_t stream) {
+  TconvKsParams p;
+  if (!tconv_ks_match(ds, count, bf16, p)) return REHR_EINVAL;   // (the caller asked tconv_ks_takes)
   switch (p.Npad / 32) {
-    case 1: rc = tconv_launch<1>(p, bf16, stream); break;
-    case 2: rc = tconv_launch<2>(p, bf16, stream); break;
-    case 3: rc = tconv_launch<3>(p, bf16, stream); break;
-    default: rc = tconv_launch<4>(p, bf16, stream); break;
+    case 1: return tconv_launch<1>(p, bf16, stream);
+    case 2: return tconv_launch<2>(p, bf16, stream);
+    case 3: return tconv_launch<3>(p, bf16, stream);
+    default: return tconv_launch<4>(p, bf16, stream);
   }
-  if (rc != REHR_OK) return rc;
-  REHR_LAUNCH_CHECK();
-  return REHR_OK;
 }

@@ -404,14 +404,37 @@ def _attach_ws(descs, n, needs, sigs, wp):
     return f.out
 
 
-def _gg_tag(d):
+def _gg_tag(arr, n=1, bf16=False):
+    """Shape of the call and, in brackets, the kernel the library runs for it: the Winograd route of a descriptor that
+    carries scratch, else the direct kernel(s) of the parts.  Evaluated by _timed only while a profile is running."""
+    d = arr[0]
+    name = _ROUTE_NAMES.get(wino_route(d)[0]) if d.wino_ws else None
+    if name is None:
+        try:
+            kinds = [_DIRECT_NAMES[bf16].get(r, "none") for r in direct_route(arr, n, bf16)]
+            name = "+".join(sorted(set(kinds), key=kinds.index))     # each kernel once, in part order
+        except L.RehrsegHipError:                                    # (the launch has raised the same error already)
+            name = "invalid"
     return (f"N{d.N} {d.Cin}->{d.Cout} lattice {d.Ld}x{d.Lh}x{d.Lw} stride {d.sd}{d.sh}{d.sw} "
-            f"taps {d.td.count}x{d.th.count}x{d.tw.count}" + (" +x2" if d.x2 else "") +
-            (" [" + _ROUTE_NAMES.get(wino_route(d)[0], "direct") + "]" if d.wino_ws else ""))
+            f"taps {d.td.count}x{d.th.count}x{d.tw.count}" + (" +x2" if d.x2 else "") + f" [{name}]")
 
 
 _ROUTE_NAMES = {L.GG_ROUTE_FLAT8: "flat8", L.GG_ROUTE_W32P: "w32p", L.GG_ROUTE_BIG8: "big8", L.GG_ROUTE_SMALL: "small",
                 L.GG_ROUTE_FLAT22: "flat22", L.GG_ROUTE_REGION22: "region22"}
+# (kind, variant) of rehr_gather_gemm_direct_route -> kernel name, fp32 / bf16
+_DIRECT_NAMES = {False: {(L.GG_DIRECT_GENERIC, 0): "generic", (L.GG_DIRECT_TCONV_KS, 0): "tconv_ks",
+                         (L.GG_DIRECT_HALO, 1): "halo bn64", (L.GG_DIRECT_HALO, 2): "halo bn32"},
+                 True: {(L.GG_DIRECT_GENERIC, 0): "generic", (L.GG_DIRECT_TCONV_KS, 0): "tconv_ks",
+                        (L.GG_DIRECT_HALO, 1): "halo 4x8x16", (L.GG_DIRECT_HALO, 2): "halo 8x8x8",
+                        (L.GG_DIRECT_HALO, 3): "halo 2x16x16"}}
+
+
+def direct_route(descs, count, bf16):
+    """[(kind, variant)] per part of rehr_gather_gemm_direct_route: the direct kernel (L.GG_DIRECT_*) that a call of the
+    fp32 / bf16 multi entry point with these `count` descriptors runs for each part no Winograd kernel takes."""
+    out = (C.c_int32 * count)()
+    L.check(L.load().rehr_gather_gemm_direct_route(descs, count, int(bool(bf16)), out), "rehr_gather_gemm_direct_route")
+    return [(r & 255, (r >> 8) & 255) for r in out]
 
 
 def wino_route(d):
@@ -438,12 +461,12 @@ def gather_gemm(*args):
     d = L.GatherGemmDesc()
     flops = _gg_desc(d, *args)
     if args[0].dtype == torch.bfloat16:
-        with _timed("gather_gemm_bf16", flops, lambda: _gg_tag(d)):
+        with _timed("gather_gemm_bf16", flops, lambda: _gg_tag((L.GatherGemmDesc * 1)(d), bf16=True)):
             L.check(L.load().rehr_gather_gemm_bf16(C.byref(d), _stream()), "rehr_gather_gemm_bf16")
         return
     arr = (L.GatherGemmDesc * 1)(d)
     keep = _attach_ws(arr, 1, [_gg_desc.need], [_gg_desc.sig], args[11])
-    with _timed(_gg_family(arr[0]), flops, lambda: _gg_tag(arr[0])):
+    with _timed(_gg_family(arr[0]), flops, lambda: _gg_tag(arr)):
         L.check(L.load().rehr_gather_gemm_multi_f32(arr, 1, _stream()), "rehr_gather_gemm_f32")
     del keep
 
@@ -459,12 +482,12 @@ def gather_gemm_multi(calls):
         needs.append(_gg_desc.need)
         sigs.append(_gg_desc.sig)
     if calls[0][0].dtype == torch.bfloat16:
-        with _timed("gather_gemm_bf16", flops, lambda: f"{len(calls)} parts of " + _gg_tag(arr[0])):
+        with _timed("gather_gemm_bf16", flops, lambda: f"{len(calls)} parts of " + _gg_tag(arr, len(calls), bf16=True)):
             L.check(L.load().rehr_gather_gemm_multi_bf16(arr, len(calls), _stream()), "rehr_gather_gemm_multi_bf16")
         return
     keep = _attach_ws(arr, len(calls), needs, sigs, calls[0][11])   # every part its own scratch: ONE launch runs them all
     with _timed(_gg_family(arr[0]) if all(arr[i].wino_ws for i in range(len(calls))) else "gather_gemm", flops,
-                lambda: f"{len(calls)} parts of " + _gg_tag(arr[0])):
+                lambda: f"{len(calls)} parts of " + _gg_tag(arr, len(calls))):
         L.check(L.load().rehr_gather_gemm_multi_f32(arr, len(calls), _stream()), "rehr_gather_gemm_multi_f32")
     del keep
 

@@ -35,6 +35,7 @@ DBG_GG_NO_TCONV_KS = 128
 DBG_GG_SLICE_MAJOR = 256
 GG_ROUTE_NONE, GG_ROUTE_FLAT8, GG_ROUTE_W32P, GG_ROUTE_BIG8 = 0, 1, 2, 3      # rehr_gather_gemm_wino_route, low byte
 GG_ROUTE_SMALL, GG_ROUTE_FLAT22, GG_ROUTE_REGION22 = 4, 5, 6
+GG_DIRECT_NONE, GG_DIRECT_GENERIC, GG_DIRECT_HALO, GG_DIRECT_TCONV_KS = 0, 1, 2, 3   # rehr_gather_gemm_direct_route, low byte
 
 _i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
 _vp = C.c_void_p
@@ -113,6 +114,7 @@ _P_GG, _P_WG, _P_DC = C.POINTER(GatherGemmDesc), C.POINTER(WgradDesc), C.POINTER
 PROTOTYPES = {
     "rehr_gather_gemm_wino_bytes": (_i64, [_P_GG]),
     "rehr_gather_gemm_wino_route": (C.c_int, [_P_GG]),
+    "rehr_gather_gemm_direct_route": (C.c_int, [_P_GG, _i32, _i32, C.POINTER(_i32)]),
     "rehr_gather_gemm_f32": (C.c_int, [_P_GG, _vp]),
     "rehr_gather_gemm_multi_f32": (C.c_int, [_P_GG, _i32, _vp]),
     "rehr_gather_gemm_bf16": (C.c_int, [_P_GG, _vp]),

@@ -119,20 +119,29 @@ def test_weight_gradient_bf16(case):
     assert relmax(db, dz.double().sum((0, 2, 3, 4))) < 1e-4
 
 
-HALO_CASES = [  # shapes the LDS halo-brick kernel takes: (N, Cin, Cout, D, H, W, kernel, pad)
-    (1, 32, 32, 8, 16, 32, (3, 3, 3), (1, 1, 1)),      # BN 32: brick 4x8x16, one block per CU
-    (2, 32, 32, 5, 32, 32, (1, 3, 3), (0, 1, 1)),      # BN 32: brick 2x16x16? (Ld 5 -> 4x8x16 pads 1.6x) / 1x3x3 taps
-    (1, 64, 64, 4, 16, 32, (3, 3, 3), (1, 1, 1)),      # BN 64: brick 2x8x16
-    (1, 64, 64, 8, 8, 8, (3, 3, 3), (1, 1, 1)),        # BN 64: brick 4x8x8
-    (1, 128, 128, 4, 16, 16, (3, 3, 3), (1, 1, 1)),    # BN 128: brick 2x8x8, 4 chunks
-    (1, 48, 96, 6, 16, 32, (3, 3, 3), (1, 1, 1)),      # half-filled last chunk, padded N (96 -> 3 x 32)
-    (2, 320, 320, 4, 8, 8, (3, 3, 3), (1, 1, 1)),      # 10 chunks, 5 channel tiles of 64
+# (N, Cin, Cout, D, H, W, kernel, pad, the kernel of the forward, the kernel of the input gradient): the bricks 4x8x16,
+# 8x8x8 and (1x3x3 taps) 2x16x16 are tried in this order and taken up to 1.3x padding; "generic": declined, or the call is
+# split into tap-range parts (ops._tap_split: few tiles, T x Cin >= 2048), which stay together in the generic grid
+HALO_CASES = [
+    (1, 32, 32, 8, 16, 32, (3, 3, 3), (1, 1, 1), "halo 4x8x16", "halo 4x8x16"),     # exact
+    (2, 32, 32, 5, 32, 32, (1, 3, 3), (0, 1, 1), "halo 2x16x16", "halo 2x16x16"),   # Ld 5: 4x8x16 and 8x8x8 pad 1.6x; 2x16x16 1.2x
+    (1, 64, 64, 4, 16, 32, (3, 3, 3), (1, 1, 1), "halo 4x8x16", "halo 4x8x16"),     # two channel tiles
+    (1, 64, 64, 8, 8, 8, (3, 3, 3), (1, 1, 1), "halo 8x8x8", "halo 8x8x8"),         # W 8 < 16
+    (1, 128, 128, 4, 16, 16, (3, 3, 3), (1, 1, 1), "generic", "generic"),           # 6 tap-range parts
+    (1, 48, 96, 6, 16, 32, (3, 3, 3), (1, 1, 1), "generic", "generic"),             # D 6 -> 8 pads 1.333x; dgrad: 6 parts
+    (2, 320, 320, 4, 8, 8, (3, 3, 3), (1, 1, 1), "generic", "generic"),             # 6 tap-range parts
+    (1, 48, 96, 8, 16, 32, (3, 3, 3), (1, 1, 1), "halo 4x8x16", "generic"),         # half-filled second chunk, Npad 96; dgrad: 6 parts
+    # 10 chunks, 10 channel tiles, W 40 -> 48 (1.2x); 200 generic blocks > 160, so no tap split
+    (1, 320, 320, 8, 16, 40, (3, 3, 3), (1, 1, 1), "halo 4x8x16", "halo 4x8x16"),
 ]
 
 
 @pytest.mark.parametrize("case", HALO_CASES)
 def test_halo_brick_kernel_matches_gather_kernel_and_torch(case):
+    import route_probe
     from rehrseg_amd import hip_backend
+    fwd_kernel, dgrad_kernel = case[8:]
+    case = case[:8]
     N, Cin, Cout, D, H, W, K, p = case
     g = torch.Generator().manual_seed(sum(case[:6]) + 3)
     x = act((N, Cin, D, H, W), g)
@@ -143,11 +152,13 @@ def test_halo_brick_kernel_matches_gather_kernel_and_torch(case):
     for halo in (True, False):
         hip_backend.USE_HALO_BF16 = halo
         try:
-            y, stats = ops.conv_forward(x, None, w, b, cfg, ops.ACT_LRELU, 0.1, 2)
-            dz = act(tuple(y.shape), torch.Generator().manual_seed(1))
-            dx, _ = ops.conv_dgrad(dz, w, (D, H, W), Cin, 0, cfg)
+            with route_probe.launches() as seen:
+                y, stats = ops.conv_forward(x, None, w, b, cfg, ops.ACT_LRELU, 0.1, 2)
+                dz = act(tuple(y.shape), torch.Generator().manual_seed(1))
+                dx, _ = ops.conv_dgrad(dz, w, (D, H, W), Cin, 0, cfg)
         finally:
             hip_backend.USE_HALO_BF16 = True
+        assert seen.kernels("gather_gemm_bf16") == ([fwd_kernel, dgrad_kernel] if halo else ["generic"] * 2), (halo, seen)
         res[halo] = (y.float(), stats.clone(), dx.float())
     wq = w.to(BF).double()
     ref = F.leaky_relu(F.conv3d(x.double(), wq, b.double(), 1, p), 0.1)

@@ -67,14 +67,17 @@ def test_conv3d(Cin, Cout, K, stride, pad, dims):
          lambda x, w, b: F.leaky_relu(F.conv3d(x, w, b, stride, pad), 0.2), [x, w, b], [True, True, True])
 
 
-HALO = [  # shapes the halo-tile kernel takes (stride 1, Cout <= 64, brick-friendly extents)
-    (64, 64, (3, 3, 3), (1, 1, 1), (1, 4, 16, 24)),
-    (32, 32, (3, 3, 3), (1, 1, 1), (2, 2, 8, 16)),
-    (96, 64, (3, 3, 3), (1, 1, 1), (1, 6, 16, 16)),
-    (16, 32, (3, 3, 3), (1, 1, 1), (1, 4, 8, 8)),
-    (32, 16, (3, 3, 3), (1, 1, 1), (1, 4, 16, 8)),
-    (32, 32, (1, 3, 3), (0, 1, 1), (2, 2, 16, 16)),
-    (64, 64, (3, 3, 3), (1, 1, 1), (1, 5, 17, 23)),   # ragged edges: masked rows
+HALO = [  # stride 1; last column: the kernel of the forward and of the input gradient (2 x 8 x 8 bricks, <= 1.3x, Npad <= 64)
+    (64, 64, (3, 3, 3), (1, 1, 1), (1, 4, 16, 24), "halo bn64"),
+    (32, 32, (3, 3, 3), (1, 1, 1), (2, 2, 8, 16), "halo bn32"),
+    # forward: three depth-tap parts (ops._tap_split) of 1x3x3 taps, one halo launch each, 3 chunks; dgrad: Npad 96 > 64
+    (96, 64, (3, 3, 3), (1, 1, 1), (1, 6, 16, 16), ("halo bn64", "generic")),
+    (16, 32, (3, 3, 3), (1, 1, 1), (1, 4, 8, 8), "halo bn32"),
+    (32, 16, (3, 3, 3), (1, 1, 1), (1, 4, 16, 8), "halo bn32"),
+    (32, 32, (1, 3, 3), (0, 1, 1), (2, 2, 16, 16), "halo bn32"),
+    (64, 64, (3, 3, 3), (1, 1, 1), (1, 5, 17, 23), "generic"),    # bricks 6 x 24 x 24 pad 1.77x: declined
+    (64, 64, (3, 3, 3), (1, 1, 1), (1, 7, 15, 23), "halo bn64"),  # ragged on all three axes (1.27x): masked rows; 400 halo rows
+    (32, 32, (3, 3, 3), (1, 1, 1), (1, 4, 15, 23), "halo bn32"),  # ragged rows and columns (1.11x)
 ]
 
 
@@ -220,14 +223,18 @@ def test_winograd_virtual_concat_instnorm():
     assert hip_backend.wino_launches > before
 
 
-@pytest.mark.parametrize("Cin,Cout,K,pad,dims", HALO)
+@pytest.mark.parametrize("Cin,Cout,K,pad,dims", [c[:5] for c in HALO])
 def test_halo_tile_conv(Cin, Cout, K, pad, dims, no_winograd):
+    import route_probe
+    kernel = {c[:5]: c[5] for c in HALO}[(Cin, Cout, K, pad, dims)]
     N, D, H, W = dims
     x = _mk(N, Cin, D, H, W, seed=50)
     w = _mk(Cout, Cin, *K, seed=51) / (Cin * K[0] * K[1] * K[2]) ** 0.5
     b = _mk(Cout, seed=52)
-    _run(lambda x, w, b: ops.fused_conv3d(x, w, b, 1, pad, act=ops.ACT_RELU),
-         lambda x, w, b: torch.relu(F.conv3d(x, w, b, 1, pad)), [x, w, b], [True, True, True])
+    with route_probe.launches() as seen:
+        _run(lambda x, w, b: ops.fused_conv3d(x, w, b, 1, pad, act=ops.ACT_RELU),
+             lambda x, w, b: torch.relu(F.conv3d(x, w, b, 1, pad)), [x, w, b], [True, True, True])
+    assert seen.kernels("gather_gemm") == (list(kernel) if isinstance(kernel, tuple) else [kernel] * 2), seen   # forward, dgrad
 
 
 def test_halo_tile_conv_virtual_concat_instnorm(no_winograd):
@@ -750,6 +757,11 @@ def test_pack_weights(A, B, K, dtype):
         assert not got[:, A:].any()
 
 
+# the fp32 kernel per (Cin, Cout): tconv_ks takes Cin <= 64 in fp32 (with 128 input channels it is one block per CU and the
+# generic grid is faster); bf16 takes all of them
+TCONV_KS_F32 = {(64, 32): "tconv_ks", (128, 64): "generic", (32, 48): "tconv_ks", (96, 128): "generic", (128, 96): "generic"}
+
+
 @pytest.mark.parametrize("mixed", [False, True])
 @pytest.mark.parametrize("Cin,Cout,stride,dims,bias", [(64, 32, (2, 2, 2), (2, 5, 12, 20), True),     # 2400 voxels: ragged last tile
                                                         (128, 64, (1, 2, 2), (1, 6, 16, 16), True),
@@ -758,7 +770,9 @@ def test_pack_weights(A, B, K, dtype):
                                                         (128, 96, (2, 1, 2), (2, 3, 5, 6), True)])
 def test_transposed_conv_kernel_equals_stride_fused_kernel(Cin, Cout, stride, dims, bias, mixed, monkeypatch):
     """tconv_ks.hip (input tile staged once, all stride phases in one block) against the generic one-block-per-(tile, phase)
-    grid and against fp64 on the same operands: forward of nnU-Net's UNetDecoder.transpconvs (seg_model.py:35)."""
+    grid and against fp64 on the same operands: forward of nnU-Net's UNetDecoder.transpconvs (seg_model.py:35).  The
+    launches' tags say which kernel ran; where fp32 declines, both arms are the generic grid."""
+    import route_probe
     from rehrseg_amd import hip_backend as hb
     N, D, H, W = dims
     dt = torch.bfloat16 if mixed else torch.float32
@@ -769,7 +783,9 @@ def test_transposed_conv_kernel_equals_stride_fused_kernel(Cin, Cout, stride, di
     out = {}
     for flag in (True, False):
         monkeypatch.setattr(hb, "USE_TCONV_KS", flag)
-        out[flag] = ops.conv_forward(x, None, w, b, cfg, ops.ACT_NONE, 0.0, 0)[0]
+        with route_probe.launches() as seen:
+            out[flag] = ops.conv_forward(x, None, w, b, cfg, ops.ACT_NONE, 0.0, 0)[0]
+        assert seen.kernels() == [("tconv_ks" if mixed else TCONV_KS_F32[Cin, Cout]) if flag else "generic"], seen
     assert out[True].dtype == dt
     _close(out[True].float(), out[False].double().cpu(), 2.0 ** -7 if mixed else 1e-5)
     wq = w.to(dt).double().cpu() if mixed else w.double().cpu()

@@ -14,8 +14,8 @@ Part A (test_layer_*): one case per distinct layer -- encoder entry and second c
 transposed convs, two-source convs and second convs, the 1x1x1 logits conv.  Stages 3-5 run at their exact lattice;
 stages 0-2 keep the full width and two 16-row region rows and are cut in H and D as far as the routing stays what it
 is at the full lattice: the Python-side picks (ops.choose_tile, the part count of ops._tap_split, ops.pad_rows) and a
-restatement of the library's acceptance rules (_wino_fwd, _halo_bf16, _wino_wgrad, _tconv_ks below; read from
-wino_region_plan, plan_flat8, halo_conv_bf16_try, wino_wgrad's plan, tconv_ks_match) are asserted equal for the
+restatement of the library's acceptance rules (_wino_fwd and _wino_wgrad below, read from wino_region_plan, plan_flat8
+and wino_wgrad's plan; _halo_bf16 and _tconv_ks ask the library's route query) are asserted equal for the
 two lattices, and test_reduced_lattice_takes_the_kernels_of_the_full_lattice runs the fp32 layer at the full lattice on
 the device and compares the Winograd launch counters.
 Tolerances are the neighbouring suites': fp32 1e-4 of the reference's max (test_kernels_gpu.py); bf16 without
@@ -41,8 +41,10 @@ import torch
 import torch.nn.functional as F
 
 from oracle.bf16_emul import Bf16Emu
+from direct_plan_cases import c3, make, tphases
 from oracle.segmodel_oracle import ANISO_PLAN
-from rehrseg_amd import ops
+from rehrseg_amd import hip_backend, ops
+from rehrseg_amd import lib as L
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -200,12 +202,9 @@ def _wino_fwd(lat, Npad, N, kd):
 
 
 def _halo_bf16(lat, kd):
-    """bf16, unit-stride 3x3 plane taps: the brick halo_conv_bf16_try settles on (<= 1.3x padding), or None."""
-    Ld, Lh, Lw = lat
-    for bd, bh, bw in [(4, 8, 16), (8, 8, 8)] + ([(2, 16, 16)] if kd == 1 else []):
-        if Ld >= (bd + 1) // 2 and Lh >= bh and Lw >= bw and _up(Ld, bd) * _up(Lh, bh) * _up(Lw, bw) * 10 <= Ld * Lh * Lw * 13:
-            return (bd, bh, bw)
-    return None
+    """bf16, unit-stride 3x3 plane taps: the brick the library settles on (rehr_gather_gemm_direct_route), or None."""
+    kind, variant = hip_backend.direct_route(make([c3(BATCH, 32, 32, tuple(lat), kd=kd)]), 1, True)[0]
+    return {1: (4, 8, 16), 2: (8, 8, 8), 3: (2, 16, 16)}[variant] if kind == L.GG_DIRECT_HALO else None
 
 
 def _wino_wgrad(lat, N, Ca, Cg):
@@ -221,7 +220,8 @@ def _wino_wgrad(lat, N, Ca, Cg):
 
 
 def _tconv_ks(Cin, Npad, bf16):
-    return Cin % 32 == 0 and Cin <= (128 if bf16 else 64) and Npad % 32 == 0 and Npad <= 128
+    """Does tconv_ks take the four phases of a (1, 2, 2) transposed convolution Cin -> Npad (the same query)?"""
+    return hip_backend.direct_route(make(tphases(Cin, Npad, (4, 8, 8), (1, 2, 2))), 4, bf16)[0][0] == L.GG_DIRECT_TCONV_KS
 
 
 def _parts(p):
@@ -497,8 +497,10 @@ def test_full_lattice_winograd_against_direct_kernels_fp32(name):
 def test_full_lattice_halo_brick_against_gather_kernel_bf16(name):
     """The bf16 legs of the same layers: LDS halo brick against the gather kernel (USE_HALO_BF16), brick against slab
     weight gradient (USE_WINOGRAD_WGRAD = False -> REHR_DBG_WGRAD_DIRECT).  Bars of
-    test_halo_brick_kernel_matches_gather_kernel_and_torch / test_brick_weight_gradient_bf16_matches_slab_kernel_and_torch;
-    no counter tells these kernels apart (the two runs of a pair differ only by the debug flag they carry)."""
+    test_halo_brick_kernel_matches_gather_kernel_and_torch / test_brick_weight_gradient_bf16_matches_slab_kernel_and_torch.
+    The tags of the profiled launches tell the conv kernels apart: forward and input gradient run the 4x8x16 halo brick by
+    default and the generic kernel with REHR_DBG_GG_NO_HALO."""
+    import route_probe
     from rehrseg_amd import hip_backend as hb
     _, _, (Cc, _), _, K, _, lat = PLAN_LAYERS[name]
     assert _halo_bf16(lat, K[0]) == (4, 8, 16)
@@ -513,8 +515,10 @@ def test_full_lattice_halo_brick_against_gather_kernel_bf16(name):
     try:
         for flag in (False, True):
             hb.USE_HALO_BF16 = hb.USE_WINOGRAD_WGRAD = flag
-            y, st = ops.conv_forward(x, None, w, b, cfg, ops.ACT_LRELU, 0.1, 2)
-            dx = ops.conv_dgrad(dz, w, lat, Cc, 0, cfg)[0]
+            with route_probe.launches() as seen:
+                y, st = ops.conv_forward(x, None, w, b, cfg, ops.ACT_LRELU, 0.1, 2)
+                dx = ops.conv_dgrad(dz, w, lat, Cc, 0, cfg)[0]
+            assert seen.kernels("gather_gemm_bf16") == ["halo 4x8x16" if flag else "generic"] * 2, (flag, seen)
             dw, _ = ops.conv_wgrad(dz, x, None, w, cfg, False)
             out[flag] = (y, st, dx, dw)
     finally:
@@ -529,7 +533,8 @@ def test_full_lattice_halo_brick_against_gather_kernel_bf16(name):
 def test_full_lattice_tconv_ks_against_generic_grid(name, mixed, monkeypatch):
     """The decoder's kernel = stride transposed convs that tconv_ks.hip takes (64 -> 32 in both precisions, 128 -> 64 in
     bf16) at 2 x C x (real lattice) against the one-block-per-(tile, phase) grid: 1e-5 of max in fp32, 2^-7 in bf16
-    (test_transposed_conv_kernel_equals_stride_fused_kernel).  No counter tells the two apart."""
+    (test_transposed_conv_kernel_equals_stride_fused_kernel).  The tags of the profiled launches tell the two apart."""
+    import route_probe
     from rehrseg_amd import hip_backend as hb
     _, _, (Cin, _), Cout, K, s, lat = PLAN_LAYERS[name]
     assert _tconv_ks(Cin, ops.pad_rows(Cout), mixed)
@@ -540,7 +545,9 @@ def test_full_lattice_tconv_ks_against_generic_grid(name, mixed, monkeypatch):
     out = {}
     for flag in (True, False):
         monkeypatch.setattr(hb, "USE_TCONV_KS", flag)
-        out[flag] = ops.conv_forward(x, None, w, b, cfg, ops.ACT_NONE, 0.0, 0)[0]
+        with route_probe.launches() as seen:
+            out[flag] = ops.conv_forward(x, None, w, b, cfg, ops.ACT_NONE, 0.0, 0)[0]
+        assert seen.kernels() == ["tconv_ks" if flag else "generic"], (flag, seen)
     assert tuple(out[True].shape[2:]) == _out_lat(lat, K, s, True)
     _check(f"{name} full lattice tconv_ks vs generic {'bf16' if mixed else 'fp32'}",
            {"y": _dev_relmax(out[True], out[False])}, {"y": 2.0 ** -7 if mixed else 1e-5})
