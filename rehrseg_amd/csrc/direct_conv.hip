@@ -728,7 +728,7 @@ __global__ __launch_bounds__(256) void small_cout_fwd_cg_kernel(const rehr_direc
 }
 
 // weight gradient, same lane mapping: a block owns (kd, kh) and a strip of output rows;
-// lane = (w position, channel quad); sums go through LDS atomics once per block.
+// lane = (w position, channel quad); sums are combined once per block, in a fixed order.
 template <int CO, int CG>
 __global__ __launch_bounds__(256) void small_cout_wgrad_cg_kernel(const rehr_direct_conv_desc d,
                                                                   float* __restrict__ slab, int rows_per_block) {
@@ -777,15 +777,33 @@ __global__ __launch_bounds__(256) void small_cout_wgrad_cg_kernel(const rehr_dir
       }
     }
   }
+  // combine in a fixed order (LDS float atomics land in arrival order: two launches differed in the last bit): the
+  // lanes of a wave that share a channel quad are CG apart -> xor butterfly, then the four waves one after another
 #pragma unroll
   for (int kw = 0; kw < SC_MAXKW; ++kw)
     if (kw < d.KW)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
-        for (int c = 0; c < CO; ++c)
-          if (c < d.Cout) atomicAdd(&red[(kw * 64 + cq * 4 + e) * 4 + c], acc[kw][e][c]);
-  __syncthreads();
+        for (int c = 0; c < CO; ++c) {
+          float a = acc[kw][e][c];
+#pragma unroll
+          for (int o = CG; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
+          acc[kw][e][c] = a;
+        }
+  for (int wv = 0; wv < 4; ++wv) {
+    if ((threadIdx.x >> 6) == wv && (threadIdx.x & 63) < CG) {
+#pragma unroll
+      for (int kw = 0; kw < SC_MAXKW; ++kw)
+        if (kw < d.KW)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int c = 0; c < CO; ++c)
+              if (c < d.Cout) red[(kw * 64 + cq * 4 + e) * 4 + c] += acc[kw][e][c];
+    }
+    __syncthreads();
+  }
   const int T = d.KD * d.KH * d.KW;
   float* sb = slab + (int64_t)strip * d.Cout * d.Cin * T;
   for (int i = threadIdx.x; i < d.KW * d.Cin * d.Cout; i += 256) {
