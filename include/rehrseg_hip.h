@@ -489,6 +489,51 @@ int rehr_seg_loss_bwd_f32(const float* logits, int32_t ld, const float* target, 
                           float w_dice, float smooth, int32_t do_bg, const float* grad_out,
                           float* dlogits, int32_t ldd, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Deep supervision (nnU-Net's DeepSupervisionWrapper over the loss above, and
+ * DownsampleSegForDSTransform2 in front of it; utils/seg_utils.py:363-371, :723-725).
+ *
+ * rehr_seg_loss_ds_{fwd,bwd}_f32: the arithmetic of rehr_seg_loss_{fwd,bwd}_f32 over up
+ * to REHR_DS_MAX_LEVELS output levels of one network in ONE launch each way.  `levels`
+ * is a HOST array (copied into the kernel arguments; the library assigns every level
+ * its own range of blocks).  All levels share N and C.  A level with weight == 0 is
+ * skipped: it gets no blocks, its pointers are not read and nothing is written for it.
+ *   fwd: stats[n_levels][N*C*3 + 1], zeroed inside by one memset, one row per level laid
+ *        out as the single-level stats; the caller forms sum_l weight_l * loss_l.
+ *   bwd: dlogits_l[N][S][ldd] = *grad_out * weight_l * d(loss_l)/d(logits_l).
+ * EINVAL: n_levels outside 1..8, a null pointer of a non-skipped level, S != d*h*w,
+ * ld / ldd < C, no level with a weight; ENOSUP: C outside 2..4.
+ *
+ * rehr_label_pyramid_f32: every level of the label pyramid of one source volume
+ * src[B][z][y][x] in ONE launch: dst_l[b][k][j][i] = src[b][iz_l[k]][iy_l[j]][ix_l[i]]
+ * (order-0 resize per axis; a pure gather, the same entry point serves the labels and
+ * the uncertainty map).  iz / iy / ix are DEVICE int32 tables of d / h / w entries whose
+ * values the caller guarantees to lie inside the source axis.
+ * ------------------------------------------------------------------------- */
+#define REHR_DS_MAX_LEVELS 8
+typedef struct {
+  const float* logits;   /* [N][S][ld] (NDHWC) */
+  const float* target;   /* [N][S] float class ids */
+  const float* unc;      /* NULL or [N][S] */
+  float* dlogits;        /* bwd only: [N][S][ldd] */
+  int64_t S;             /* d * h * w */
+  int32_t d, h, w;
+  int32_t ld, ldd;
+  float weight;          /* 0: the level is skipped */
+} rehr_seg_ds_level;
+int rehr_seg_loss_ds_fwd_f32(const rehr_seg_ds_level* levels, int32_t n_levels, int32_t N, int32_t C,
+                             double* stats, void* stream);
+int rehr_seg_loss_ds_bwd_f32(const rehr_seg_ds_level* levels, int32_t n_levels, int32_t N, int32_t C,
+                             const double* stats, float w_ce, float w_dice, float smooth, int32_t do_bg,
+                             const float* grad_out, void* stream);
+typedef struct {
+  float* dst;                     /* [B][d][h][w] */
+  int32_t d, h, w;
+  const int32_t *iz, *iy, *ix;    /* device tables: source index of every output index, per axis */
+} rehr_pyramid_level;
+int rehr_label_pyramid_f32(const float* src, int32_t B, int32_t z, int32_t y, int32_t x,
+                           const rehr_pyramid_level* levels, int32_t n_levels, void* stream);
+
 /* Elementwise helpers used by the blocks above. */
 int rehr_act_fwd_f32(const float* x, float* y, int64_t n, int32_t act,
                      float slope, void* stream);

@@ -963,6 +963,94 @@ def seg_loss_bwd(logits, target, unc, stats, w_ce, w_dice, smooth, do_bg, grad_o
     return dl
 
 
+def _ds_levels(logits, targets, uncs, weights, dlogits=None):
+    """The host descriptors of one deep-supervision launch.  logits[l] (N,C,d,h,w) NDHWC float32, targets[l] / uncs[l]
+    (N,S) float32; a level whose weight is 0 is skipped and may hold None."""
+    n = len(logits)
+    if not 1 <= n <= L.DS_MAX_LEVELS or len(targets) != n or len(weights) != n or (uncs is not None and len(uncs) != n):
+        raise L.RehrsegHipError(f"deep supervision: 1..{L.DS_MAX_LEVELS} levels with one target and one weight each")
+    live = [l for l in range(n) if float(weights[l]) != 0.0]
+    if not live:
+        raise L.RehrsegHipError("deep supervision: every level has weight 0")
+    N, Cc = logits[live[0]].shape[:2]
+    arr = (L.SegDsLevel * n)()
+    for l in live:
+        x, t = logits[l], targets[l]
+        u = None if uncs is None else uncs[l]
+        _chk_dev(x, t, u)
+        if x.dtype != torch.float32 or x.dim() != 5 or tuple(x.shape[:2]) != (N, Cc) or \
+                not x.permute(0, 2, 3, 4, 1).is_contiguous():
+            raise L.RehrsegHipError("deep supervision: float32 NDHWC logits with one (N, C) over all levels")
+        d, h, w = x.shape[2:]
+        S = d * h * w
+        for name, v in (("target", t), ("uncertainty", u)):
+            if v is not None and (v.dtype != torch.float32 or tuple(v.shape) != (N, S) or not v.is_contiguous()):
+                raise L.RehrsegHipError(f"deep supervision: {name} of level {l} must be contiguous float32 ({N}, {S})")
+        arr[l].logits, arr[l].target = x.data_ptr(), t.data_ptr()
+        arr[l].unc = None if u is None else u.data_ptr()
+        arr[l].S, arr[l].d, arr[l].h, arr[l].w = S, d, h, w
+        arr[l].ld = arr[l].ldd = Cc
+        arr[l].weight = float(weights[l])
+        if dlogits is not None:
+            arr[l].dlogits = dlogits[l].data_ptr()
+    return arr, n, N, Cc
+
+
+def seg_loss_ds_fwd(logits, targets, uncs, weights):
+    """Every level of a deep-supervision loss in one launch (rehr_seg_loss_ds_fwd_f32) -> stats double
+    [levels][N*C*3 + 1], one row per level laid out as seg_loss_fwd's (rows of skipped levels are zero)."""
+    arr, n, N, Cc = _ds_levels(logits, targets, uncs, weights)
+    dev = next(x for x in logits if x is not None).device
+    stats = torch.empty((n, N * Cc * 3 + 1), dtype=torch.float64, device=dev)
+    L.check(L.load().rehr_seg_loss_ds_fwd_f32(arr, n, N, Cc, _ptr(stats), _stream()), "rehr_seg_loss_ds_fwd_f32")
+    return stats
+
+
+def seg_loss_ds_bwd(logits, targets, uncs, weights, stats, w_ce, w_dice, smooth, do_bg, grad_out):
+    """-> per level grad_out * weight * d(loss_l)/d(logits_l) in one launch; None for a skipped level."""
+    _chk_dev(grad_out, f64=(stats,))
+    dl = [None if float(w) == 0.0 else new_act(*x.shape, like=x) for x, w in zip(logits, weights)]
+    arr, n, N, Cc = _ds_levels(logits, targets, uncs, weights, dl)
+    if tuple(stats.shape) != (n, N * Cc * 3 + 1) or not stats.is_contiguous():
+        raise L.RehrsegHipError("deep supervision: stats of another launch")
+    L.check(L.load().rehr_seg_loss_ds_bwd_f32(arr, n, N, Cc, _ptr(stats), float(w_ce), float(w_dice), float(smooth),
+                                              int(do_bg), _ptr(grad_out), _stream()), "rehr_seg_loss_ds_bwd_f32")
+    return dl
+
+
+def label_pyramid(src, extents, tables):
+    """Every level of an order-0 label pyramid in one launch (rehr_label_pyramid_f32).  src: contiguous float32 device
+    tensor (..., z, y, x); extents[l] = (d, h, w); tables[l] = (iz, iy, ix) device int32 source indices of the three
+    axes, whose values the caller has checked against (z, y, x).  -> [(..., d, h, w) float32 per level]."""
+    _chk_dev(src)
+    if src.dtype != torch.float32 or not src.is_contiguous() or src.dim() < 3:
+        raise L.RehrsegHipError("label_pyramid: contiguous float32 (..., z, y, x) source")
+    n = len(extents)
+    if not 1 <= n <= L.DS_MAX_LEVELS or len(tables) != n:
+        raise L.RehrsegHipError(f"label_pyramid: 1..{L.DS_MAX_LEVELS} levels with three index tables each")
+    lead = tuple(src.shape[:-3])
+    z, y, x = src.shape[-3:]
+    B = src.numel() // (z * y * x)
+    arr = (L.PyramidLevel * n)()
+    outs = []
+    for l, (ext, tab) in enumerate(zip(extents, tables)):
+        ext = tuple(int(v) for v in ext)
+        if len(ext) != 3 or min(ext) < 1 or len(tab) != 3:
+            raise L.RehrsegHipError(f"label_pyramid: level {l} needs a positive (d, h, w) and three tables")
+        for t, k in zip(tab, ext):
+            if t.dtype != torch.int32 or t.device != src.device or tuple(t.shape) != (k,) or not t.is_contiguous():
+                raise L.RehrsegHipError(f"label_pyramid: level {l} index tables are int32 [{ext}] on the source's device")
+        out = torch.empty(lead + ext, dtype=torch.float32, device=src.device)
+        outs.append(out)
+        arr[l].dst = out.data_ptr()
+        arr[l].d, arr[l].h, arr[l].w = ext
+        arr[l].iz, arr[l].iy, arr[l].ix = (t.data_ptr() for t in tab)
+    if B == 0:
+        return outs
+    L.check(L.load().rehr_label_pyramid_f32(_ptr(src), B, z, y, x, arr, n, _stream()), "rehr_label_pyramid_f32")
+    return outs
+
+
 def bce_dice_fwd(x, t):
     """x, t dense (N, C, S) float32 -> stats (C, 4) double = {sum bce, sum p t, sum p^2, sum t^2}."""
     _chk_dev(x, t)

@@ -108,7 +108,19 @@ class PatchGatherDesc(C.Structure):
                 ("dst", _vp), ("dst_item_stride", _i64)]
 
 
-_P_GG, _P_WG, _P_DC = C.POINTER(GatherGemmDesc), C.POINTER(WgradDesc), C.POINTER(DirectConvDesc)
+DS_MAX_LEVELS = 8
+
+
+class SegDsLevel(C.Structure):
+    _fields_ = [("logits", _vp), ("target", _vp), ("unc", _vp), ("dlogits", _vp), ("S", _i64),
+                ("d", _i32), ("h", _i32), ("w", _i32), ("ld", _i32), ("ldd", _i32), ("weight", _f32)]
+
+
+class PyramidLevel(C.Structure):
+    _fields_ = [("dst", _vp), ("d", _i32), ("h", _i32), ("w", _i32), ("iz", _vp), ("iy", _vp), ("ix", _vp)]
+
+
+_P_GG, _P_WG, _P_DC =C.POINTER(GatherGemmDesc), C.POINTER(WgradDesc), C.POINTER(DirectConvDesc)
 
 # name -> (restype, argtypes); must list every function include/rehrseg_hip.h declares
 PROTOTYPES = {
@@ -201,6 +213,10 @@ PROTOTYPES = {
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),
+    "rehr_seg_loss_ds_fwd_f32": (C.c_int, [C.POINTER(SegDsLevel), _i32, _i32, _i32, _vp, _vp]),
+    "rehr_seg_loss_ds_bwd_f32": (C.c_int, [C.POINTER(SegDsLevel), _i32, _i32, _i32, _vp, _f32, _f32, _f32, _i32, _vp,
+                                           _vp]),
+    "rehr_label_pyramid_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(PyramidLevel), _i32, _vp]),
     "rehr_bce_dice_fwd_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_bce_dice_bwd_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _vp, _vp, _vp]),
     "rehr_act_fwd_f32": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _vp]),

@@ -163,13 +163,18 @@ def train_segsr_step(model_seg, model_sr, distiller, opt, img, label_lr, label_h
                      loss_hr_seg, enable_uncertainty=True, teacher_levels=(1,), grad_sync=None, zero_grad=None,
                      teacher_stream=True):
     """One iteration of the stage-2 loop (train_all.py:521-556); returns the loss tensor.
-    teacher_stream: run the frozen teacher's pass on a second HIP stream next to the student's forward."""
+    teacher_stream: run the frozen teacher's pass on a second HIP stream next to the student's forward.
+    With deep supervision (model_seg.decoder.deep_supervision, a _build_loss(True) loss_lr_seg) label_lr and
+    uncertainty_lr are the per-level lists of the data set; the teacher reads level 0."""
     model_seg.train()
+    label_levels = list(label_lr) if isinstance(label_lr, (list, tuple)) else [label_lr]
+    unc_levels = list(uncertainty_lr) if isinstance(uncertainty_lr, (list, tuple)) else []
+    label_full = label_levels[0]
     if distiller is not None:
         side = _teacher_stream(img) if teacher_stream else None
         if side is None:
             with torch.no_grad():
-                features_sr = get_intermediate_features(model_sr, img, label_lr, img.device, levels=teacher_levels)
+                features_sr = get_intermediate_features(model_sr, img, label_full, img.device, levels=teacher_levels)
             seg_lr, seg_sr, features_seg = model_seg(img, return_inetermediate_feature=True)
         else:
             # The frozen teacher's pass and the student's forward are independent once the image is z-scored (in place,
@@ -180,13 +185,13 @@ def train_segsr_step(model_seg, model_sr, distiller, opt, img, label_lr, label_h
                 normalized = zscore_normalization(img)
             side.wait_stream(main)
             with torch.cuda.stream(side), torch.no_grad():
-                features_sr = get_intermediate_features(model_sr, img, label_lr, img.device, levels=teacher_levels,
+                features_sr = get_intermediate_features(model_sr, img, label_full, img.device, levels=teacher_levels,
                                                         _normalized=normalized)
             seg_lr, seg_sr, features_seg = model_seg(img, return_inetermediate_feature=True)
             main.wait_stream(side)
             for t in features_sr.values():
                 t.record_stream(main)          # allocated on the side stream, consumed (and later freed) on the main one
-            for t in (img, label_lr, normalized):
+            for t in (img, normalized, *label_levels, *unc_levels):
                 t.record_stream(side)
     else:
         seg_lr, seg_sr = model_seg(img)

@@ -7,9 +7,10 @@ uploads them once per batch without waiting, and the kernels of csrc/augment.hip
 `rehr_axis_resample_f32` do the arithmetic (`apply`).
 
 Restated from the published behaviour of batchgenerators 0.25, scipy.ndimage and skimage (absent offline or not
-vendored), PARITY UNPINNED as `resize` and `degrade` are: the intensity transforms, Convert3DTo2D / Convert2DTo3D and
-the coordinate helpers.  What the fixtures of tools/gen_golden_augment.py pin: the spatial draw protocol and the
-warp against the reference's own augment_spatial.  Deliberate differences:
+vendored), PARITY UNPINNED as `resize` and `degrade` are: the intensity transforms, Convert3DTo2D / Convert2DTo3D,
+the coordinate helpers and the deep-supervision label pyramid (DownsampleSegForDSTransform2).
+What the fixtures of tools/gen_golden_augment.py pin: the spatial draw protocol and the warp against the reference's
+own augment_spatial.  Deliberate differences:
   * batchgenerators draws the noise variance and the blur sigma from Python's `random`; here they come from
     `np.random`, so that Python's `random` stays the patch draw protocol of train_set.py alone.
   * the noise field comes from a counter-based generator in the kernel, seeded by one `np.random.randint` draw, not
@@ -204,13 +205,24 @@ def _prefilter_taps(n, device):
 
 class TrainingTransforms:
     """get_training_transforms(...) for what REHRSeg passes: callable over keyword tensors (B, 1, z, y, x) float32 on
-    the device; `data` is augmented, the extra keys follow the spatial step only.  Items draw one after another."""
+    the device; `data` is augmented, the extra keys follow the spatial step only.  Items draw one after another.
+    With `deep_supervision_scales` the result's `seg` (and, with enable_uncertainty, the uncertainty) is a list with one
+    tensor per scale; `data` and the other keys are untouched by that step, which draws no random numbers."""
 
-    def __init__(self, patch_size_spatial, angle_x, enable_spatial, enable_uncertainty, extra_keys, rng=np.random):
+    def __init__(self, patch_size_spatial, angle_x, enable_spatial, enable_uncertainty, extra_keys, rng=np.random,
+                 deep_supervision_scales=None):
         self.patch_size_spatial = None if patch_size_spatial is None else [int(v) for v in patch_size_spatial]
         self.angle_x, self.enable_spatial = tuple(angle_x), bool(enable_spatial)
         self.enable_uncertainty, self.extra_keys = bool(enable_uncertainty), list(extra_keys)
         self.rng = rng
+        # the last step of the chain (ref :723-725): 'seg' becomes the list of its deep-supervision levels, and with
+        # enable_uncertainty the uncertainty map (the last extra key) follows through the same index maps
+        self.pyramid = None
+        if deep_supervision_scales is not None:
+            also = (self.extra_keys[-1],) if self.enable_uncertainty and self.extra_keys and \
+                self.extra_keys[-1] != "seg" else ()
+            self.pyramid = DownsampleSegForDSTransform2(deep_supervision_scales, 0, input_key="seg", output_key="seg",
+                                                        also=also)
 
     def draw(self, n):
         out = []
@@ -240,7 +252,8 @@ class TrainingTransforms:
         if self.enable_spatial:
             out.update(self._spatial(draws, flat, hb))
         out["data"] = self._intensity(draws, out["data"].contiguous(), hb)
-        return {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
+        out = {k: v.reshape(lead + tuple(v.shape[1:])) for k, v in out.items()}
+        return out if self.pyramid is None else self.pyramid(**out)
 
     # Convert3DTo2D -> MySpatialTransform -> Convert2DTo3D: (B, 1, z, y, x) -> (B, z, y, x) -> warp -> back
     def _spatial(self, draws, data, hb):
@@ -384,6 +397,83 @@ class MySpatialTransform:
         return data_dict
 
 
+# the reference's scale table of the six outputs of the 3d_fullres network, (z, y, x) per level (utils/seg_utils.py:364,
+# utils/train_set.py:67)
+DEEP_SUPERVISION_SCALES = [[1.0, 1.0, 1.0], [1.0, 0.5, 0.5], [1.0, 0.25, 0.25], [0.5, 0.125, 0.125],
+                           [0.25, 0.0625, 0.0625], [0.25, 0.03125, 0.03125]]
+
+
+def zoom_nearest_index(n_in, n_out):
+    """zoom_nearest_matrix as an index table: int32 [n_out], entry j = the input sample output j reads."""
+    if n_out < 1:
+        raise ValueError(f"order-0 resize of {n_in} samples to {n_out}: the target extent must be at least 1")
+    idx = np.argmax(zoom_nearest_matrix(n_in, n_out), axis=1).astype(np.int32)
+    assert idx.min() >= 0 and idx.max() < n_in
+    return idx
+
+
+def pyramid_extents(shape, scales):
+    """DownsampleSegForDSTransform2's target extents: np.round(extent * scale) per axis (half to even) for every level;
+    `scales` holds one number or one (z, y, x) triple per level.  An extent of 0 raises."""
+    out = []
+    for s in scales:
+        s = [float(s)] * len(shape) if np.isscalar(s) else [float(v) for v in s]
+        if len(s) != len(shape):
+            raise ValueError(f"deep supervision scale {s} for a {len(shape)}-axis label map")
+        ext = [int(v) for v in np.round(np.asarray(shape, np.float64) * np.asarray(s))]
+        if min(ext) < 1:
+            raise ValueError(f"deep supervision scale {s} leaves no voxel of a {tuple(shape)} label map: {ext}")
+        out.append(tuple(ext))
+    return out
+
+
+_index_cache = {}   # (n_in, n_out, device) -> device int32 index table of the order-0 resize
+
+
+def _cached_index(n_in, n_out, device):
+    key = (int(n_in), int(n_out), device)
+    if key not in _index_cache:
+        _index_cache[key] = _upload(zoom_nearest_index(n_in, n_out), device)
+    return _index_cache[key]
+
+
+class DownsampleSegForDSTransform2:
+    """batchgenerators' DownsampleSegForDSTransform2 for what get_training_transforms passes (order 0), restated (skimage
+    absent offline, PARITY UNPINNED): `input_key` (B, C, z, y, x) becomes under `output_key` a list with one tensor per
+    scale.  A level whose scales are all 1 is the input itself; every other level is the order-0 resize of every axis
+    (zoom_nearest_matrix: skimage resize(order=0, mode='edge', anti_aliasing=False)), all levels written by one launch
+    of rehr_label_pyramid_f32.  `also` names further keys resampled with the same index maps (the uncertainty)."""
+
+    def __init__(self, ds_scales=(1, 0.5, 0.25), order=0, input_key="seg", output_key="seg", axes=None, also=()):
+        if order != 0:
+            raise NotImplementedError("DownsampleSegForDSTransform2: order 0 only (what get_training_transforms passes)")
+        if axes is not None:
+            raise NotImplementedError("DownsampleSegForDSTransform2: axes other than the three spatial ones")
+        self.ds_scales, self.input_key, self.output_key, self.also = list(ds_scales), input_key, output_key, tuple(also)
+
+    def pyramid(self, t):
+        from .. import hip_backend as hb
+        if not t.is_cuda or t.dim() < 4:
+            raise hb.L.RehrsegHipError("deep supervision: the label pyramid is built from a (..., z, y, x) device tensor")
+        shape = tuple(t.shape[-3:])
+        extents = pyramid_extents(shape, self.ds_scales)
+        work = [l for l, s in enumerate(self.ds_scales) if not all(float(v) == 1 for v in np.atleast_1d(s))]
+        out = [t] * len(extents)
+        if work:
+            src = t.to(torch.float32).contiguous()
+            res = hb.label_pyramid(src, [extents[l] for l in work],
+                                   [tuple(_cached_index(n, m, t.device) for n, m in zip(shape, extents[l])) for l in work])
+            for l, r in zip(work, res):
+                out[l] = r
+        return out
+
+    def __call__(self, **data_dict):
+        for key_in, key_out in [(self.input_key, self.output_key)] + [(k, k) for k in self.also]:
+            if data_dict.get(key_in) is not None:
+                data_dict[key_out] = self.pyramid(data_dict[key_in])
+        return data_dict
+
+
 def get_training_transforms(patch_size, rotation_for_DA, deep_supervision_scales, mirror_axes, do_dummy_2d_data_aug,
                             order_resampling_data=3, order_resampling_seg=1, border_val_seg=-1, use_mask_for_norm=None,
                             is_cascaded=False, foreground_labels=None, regions=None, ignore_label=None,
@@ -393,7 +483,14 @@ def get_training_transforms(patch_size, rotation_for_DA, deep_supervision_scales
     def no(what):
         raise NotImplementedError(f"get_training_transforms: {what} is not used by REHRSeg and not implemented")
     if deep_supervision_scales is not None:
-        no("deep_supervision_scales")
+        # REHRSeg passes None or its one hard-coded table (utils/train_set.py:65-69), whose level weights _build_loss
+        # hard-codes next to it (utils/seg_utils.py:364-369); any other table has no weights to go with it
+        try:
+            table = [[float(v) for v in s] for s in deep_supervision_scales]
+        except TypeError:
+            table = None
+        if table != DEEP_SUPERVISION_SCALES:
+            no("deep_supervision_scales other than the reference's table (augment.DEEP_SUPERVISION_SCALES)")
     if mirror_axes is not None and len(mirror_axes) > 0:
         no("mirror_axes")
     if not do_dummy_2d_data_aug:
@@ -412,4 +509,4 @@ def get_training_transforms(patch_size, rotation_for_DA, deep_supervision_scales
     if tuple(angles.get("y", (0, 0))) != (0, 0) or tuple(angles.get("z", (0, 0))) != (0, 0):
         no("rotation about y / z (the dummy-2D path rotates in-plane only)")
     return TrainingTransforms(list(patch_size)[1:] if enable_spatial else None, angles["x"], enable_spatial,
-                              enable_uncertainty, extra_keys)
+                              enable_uncertainty, extra_keys, deep_supervision_scales=deep_supervision_scales)

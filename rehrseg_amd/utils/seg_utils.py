@@ -1,7 +1,7 @@
 """Losses and normalisation used by the two training loops, under the reference's import
 path (`utils.seg_utils`): same names, arguments and numerics as utils/seg_utils.py:137-156
 (zscore_normalization), :289-372 (RobustCrossEntropyLoss, DC_and_weighted_CE_loss,
-_build_loss) and :786-885 (DiceLoss, BCEDiceLoss).
+_build_loss, with nnunetv2's DeepSupervisionWrapper restated) and :786-885 (DiceLoss, BCEDiceLoss).
 
 The stage-2 loss (`DC_and_weighted_CE_loss`) runs as one fused HIP pass over the logits each way when
 given device tensors (`_FusedDCCE`); the torch composition below it is the same
@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .augment import MySpatialTransform, get_training_transforms  # noqa: F401  (utils/seg_utils.py:511-728)
+from .augment import (DEEP_SUPERVISION_SCALES, DownsampleSegForDSTransform2, MySpatialTransform,  # noqa: F401
+                      get_training_transforms)                                              # (utils/seg_utils.py:511-728)
 
 
 def zscore_normalization(image):
@@ -178,14 +179,125 @@ class DC_and_weighted_CE_loss(nn.Module):
         return self.weight_ce * ce_loss + self.weight_dice * dc_loss
 
 
+@functools.lru_cache(maxsize=16)
+def _ds_coefficients(weights, sizes, N, with_unc, w_ce, w_dice, device):
+    """(levels, 2) double on the device: per level the factors of its CE statistic and of its mean Dice in the weighted
+    sum.  Uploaded once per configuration, so that the sum over levels is formed without a host sync."""
+    rows = [(w * w_ce / ((N * N * S) if with_unc else (N * S)) if w != 0 else 0.0, w * w_dice)
+            for w, S in zip(weights, sizes)]
+    return _upload(torch.tensor(rows, dtype=torch.float64), torch.device(device))
+
+
+class _FusedDSDCCE(torch.autograd.Function):
+    """DeepSupervisionWrapper(DC_and_weighted_CE_loss) over device tensors: all levels in one HIP launch each way
+    (include/rehrseg_hip.h: rehr_seg_loss_ds_{fwd,bwd}_f32).  The logits are the trailing arguments.  The wrapper hands
+    in the weighted levels only: a level with weight 0 stays outside the graph, so its logits get no gradient at all
+    (a None returned here would be filled with zeros by the node that made those logits)."""
+
+    @staticmethod
+    def forward(ctx, cfg, weights, targets, uncs, *logits):
+        from .. import hip_backend as hb, ops
+        w_ce, w_dice, smooth, do_bg = cfg
+        n = len(logits)
+        N, C = logits[0].shape[:2]
+        sizes = [x.shape[2] * x.shape[3] * x.shape[4] for x in logits]
+        xs = [ops.to_cl(x.float()) for x in logits]
+        ts = [t.reshape(N, S).to(torch.float32).contiguous() for t, S in zip(targets, sizes)]
+        us = None if uncs is None else [u.reshape(N, S).to(torch.float32).contiguous() for u, S in zip(uncs, sizes)]
+        stats = hb.seg_loss_ds_fwd(xs, ts, us, weights)
+        ipg = stats[:, :-1].view(n, N, C, 3)
+        dc = (2 * ipg[..., 0] + smooth) / torch.clip(ipg[..., 2] + ipg[..., 1] + smooth, 1e-8)
+        if not do_bg:
+            dc = dc[:, :, 1:]
+        k = _ds_coefficients(tuple(weights), tuple(sizes), N, uncs is not None, w_ce, w_dice, str(stats.device))
+        loss = (k[:, 0] * stats[:, -1]).sum() - (k[:, 1] * dc.mean((1, 2))).sum()
+        ctx.save_for_backward(stats, *xs, *ts, *([] if us is None else us))
+        ctx.cfg, ctx.weights = cfg, weights
+        ctx.dtypes = [x.dtype for x in logits]
+        return loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .. import hip_backend as hb
+        stats, *saved = ctx.saved_tensors
+        n = len(ctx.weights)
+        xs, ts, us = saved[:n], saved[n:2 * n], (saved[2 * n:] or None)
+        w_ce, w_dice, smooth, do_bg = ctx.cfg
+        go = grad_out.to(torch.float32).reshape(1).contiguous()
+        dl = hb.seg_loss_ds_bwd(xs, ts, us, ctx.weights, stats, w_ce, w_dice, smooth, do_bg, go)
+        return (None, None, None, None, *[g if g.dtype == dt else g.to(dt) for g, dt in zip(dl, ctx.dtypes)])
+
+
+class DeepSupervisionWrapper(nn.Module):
+    """nnunetv2's DeepSupervisionWrapper, restated (absent offline -> parity unpinned): every positional argument is a
+    list or tuple with one entry per output level, and the result is
+        sum(weight_factors[i] * loss(*args_i) for i, args_i in enumerate(zip(*args)) if weight_factors[i] != 0).
+    zip truncates to the shortest list; a level with weight 0 is not evaluated, so its logits receive no gradient.
+    Trailing arguments that are None (the step's `uncertainty=None`) are dropped.
+
+    Over device tensors that DC_and_weighted_CE_loss would take through its fused kernel at every weighted level,
+    the whole sum is one autograd node with one HIP launch each way (`_FusedDSDCCE`); otherwise it is the Python sum
+    above over the inner loss."""
+
+    def __init__(self, loss, weight_factors=None):
+        super().__init__()
+        if weight_factors is not None and not any(x != 0 for x in weight_factors):
+            raise ValueError("At least one weight factor should be != 0.0")
+        self.weight_factors = None if weight_factors is None else tuple(float(x) for x in weight_factors)
+        self.loss = loss
+
+    def forward(self, *args):
+        while args and args[-1] is None:
+            args = args[:-1]
+        if not all(isinstance(a, (tuple, list)) for a in args):
+            raise TypeError("DeepSupervisionWrapper: every argument is a list or tuple with one entry per output level "
+                            f"(the uncertainty as well: one map per level), got {[type(a).__name__ for a in args]}")
+        levels = list(zip(*args))
+        weights = (1.0,) * len(levels) if self.weight_factors is None else self.weight_factors
+        if len(weights) < len(levels):
+            raise ValueError(f"{len(levels)} output levels but only {len(weights)} weight factors")
+        weights = weights[:len(levels)]
+        live = [i for i, w in enumerate(weights) if w != 0]
+        if not live:
+            raise ValueError("every level present carries weight 0")
+        for i in live:
+            x, y = levels[i][0], levels[i][1]
+            if tuple(x.shape[2:]) != tuple(y.shape[-(x.dim() - 2):]) or x.shape[0] != y.shape[0]:
+                raise ValueError(f"level {i}: logits {tuple(x.shape)} do not match the label level {tuple(y.shape)}")
+        if self._fusable(levels, live):
+            inner = self.loss
+            cfg = (float(inner.weight_ce), float(inner.weight_dice), float(inner.dc.smooth), bool(inner.dc.do_bg))
+            # only the weighted levels enter the node: a gradient of None returned for an input would be turned into
+            # zeros by the node that produced those logits, and the optimizer would then decay that head
+            used = [levels[i] for i in live]
+            uncs = [lv[2] for lv in used] if len(args) == 3 else None
+            return _FusedDSDCCE.apply(cfg, tuple(weights[i] for i in live), [lv[1] for lv in used], uncs,
+                                      *[lv[0] for lv in used])
+        return sum(weights[i] * self.loss(*levels[i]) for i in live)
+
+    def _fusable(self, levels, live):
+        from ..lib import DS_MAX_LEVELS
+        if not isinstance(self.loss, DC_and_weighted_CE_loss) or not 2 <= len(levels[0]) <= 3 or \
+                len(levels) > DS_MAX_LEVELS:
+            return False
+        first = levels[live[0]][0]
+        return all(self.loss._fusable(*levels[i], *([None] * (3 - len(levels[i])))) and
+                   tuple(levels[i][0].shape[:2]) == tuple(first.shape[:2]) and levels[i][0].device == first.device
+                   for i in live)
+
+
 def _build_loss(enable_deep_supervision=False, weight_dice=1):
-    """ref :353-372 without the DeepSupervisionWrapper branch (the reference trains with
-    enable_deep_supervision=False, train_all.py:471)."""
-    if enable_deep_supervision:
-        raise NotImplementedError("deep supervision wrapper (nnunetv2) is not part of the hot path")
-    return DC_and_weighted_CE_loss({"batch_dice": False, "smooth": 1e-5, "do_bg": False, "ddp": False},
+    """ref :353-372.  With enable_deep_supervision the loss is wrapped for the network's per-stage outputs: weights
+    1 / 2**i over the reference's six scales, the last set to 0, normalised to sum 1 (:363-369)."""
+    loss = DC_and_weighted_CE_loss({"batch_dice": False, "smooth": 1e-5, "do_bg": False, "ddp": False},
                                    {"reduction": "none"}, weight_ce=1, weight_dice=weight_dice, ignore_label=None,
                                    dice_class=SoftDiceLoss)
+    if enable_deep_supervision:
+        weights = np.array([1 / (2 ** i) for i in range(len(DEEP_SUPERVISION_SCALES))])
+        weights[-1] = 0
+        weights = weights / weights.sum()
+        loss = DeepSupervisionWrapper(loss, weights)
+    return loss
 
 
 def compute_per_channel_dice(input, target, epsilon=1e-6, weight=None):

@@ -26,6 +26,7 @@ import torch
 
 from .. import hip_backend as hb
 from .pad import get_pads
+from .augment import DEEP_SUPERVISION_SCALES
 from .seg_utils import get_training_transforms, zscore_normalization
 
 _ROTATION_FOR_DA = {"x": (-np.pi, np.pi), "y": (0, 0), "z": (0, 0)}  # utils/train_set.py:61, :260
@@ -322,7 +323,7 @@ class _DeviceSet(torch.utils.data.Dataset):
                 "training process (DataLoader(num_workers=0, pin_memory=False), or ds.batch(indices)), not from "
                 "DataLoader worker processes")
         out = self._run([self._plan(i)])
-        return tuple(o[0] if torch.is_tensor(o) else o for o in out)
+        return tuple(o[0] if torch.is_tensor(o) else [u[0] for u in o] if isinstance(o, list) else o for o in out)
 
 
 # ----------------------------------------------------------------------------- stage 2: image / label / uncertainty patches
@@ -332,11 +333,15 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
     the H5 files when given.  `train_transform` stands where the
     reference calls its batchgenerators chain (:64-84): "nnunet" builds that chain on the device (utils/augment.py;
     in-plane output `target_patch_size`), a callable over the keyword tensors data / seg / seg_sr / uncertainty is
-    used as given, None (default) is the identity."""
+    used as given, None (default) is the identity.
+    `deep_supervision` (port only: the reference hard-codes a local, :65-69): the reference's scale table goes to the
+    transform chain ("nnunet"), or, with another or no train_transform, to the pyramid step alone behind it; label_lr
+    (and uncertainty_lr) then come back as lists with one (1, d, h, w) tensor per level ((B, 1, d, h, w) from `batch`).
+    The step draws no random numbers."""
 
     def __init__(self, image_path, split_subjects, slice_thickness, target_thickness, patch_size_ori, target_patch_size,
                  random_flip=False, uncertainty=False, preload=True, norm=True, device=None, volumes=None,
-                 train_transform=None):
+                 train_transform=None, deep_supervision=False):
         self.image_path, self.patch_size = image_path, list(patch_size_ori)
         self.slice_thickness, self.target_thickness = slice_thickness, target_thickness
         self.separation = int(slice_thickness / target_thickness)
@@ -346,10 +351,16 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
             if train_transform != "nnunet":
                 raise ValueError(f"train_transform: 'nnunet', a callable or None, got {train_transform!r}")
             train_transform = get_training_transforms(
-                list(target_patch_size)[::-1], _ROTATION_FOR_DA, None, None, True, order_resampling_data=3,
+                list(target_patch_size)[::-1], _ROTATION_FOR_DA, DEEP_SUPERVISION_SCALES if deep_supervision else None,
+                None, True, order_resampling_data=3,
                 order_resampling_seg=1, use_mask_for_norm=[False], is_cascaded=False, foreground_labels=[1],
                 regions=None, ignore_label=None, enable_uncertainty=uncertainty,
                 extra_keys=["seg", "seg_sr", "uncertainty"] if uncertainty else ["seg", "seg_sr"])
+            self._pyramid = None
+        else:
+            from .augment import DownsampleSegForDSTransform2
+            self._pyramid = DownsampleSegForDSTransform2(
+                DEEP_SUPERVISION_SCALES, 0, also=("uncertainty",) if uncertainty else ()) if deep_supervision else None
         self.train_transform = train_transform
         self.device = self._check_device(device)
         self.imgs, self.labels, self.uncertainties = [], [], []
@@ -413,8 +424,11 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
             data["uncertainty"] = _gather(lr, [self.uncertainties[i] for i in ids], -0.99 / 255.0, 1.0)
         if self.train_transform is not None:
             data = self.train_transform(**data)
-        # the per-item tensors are (1, 1, z, y, x); .squeeze(0) leaves (1, z, y, x) (:149-158)
-        sq = lambda t: t.squeeze(1)  # noqa: E731
+        if self._pyramid is not None:
+            data = self._pyramid(**data)
+        # the per-item tensors are (1, 1, z, y, x); .squeeze(0) leaves (1, z, y, x) (:149-158).  With deep supervision
+        # 'seg' (and the uncertainty) is a list, which the reference's .squeeze(0) cannot take: every level is squeezed
+        sq = lambda t: [u.squeeze(1) for u in t] if isinstance(t, (list, tuple)) else t.squeeze(1)  # noqa: E731
         unc = sq(data["uncertainty"]) if self.uncertainty else 0
         return sq(data["data"]), sq(data["seg"]), sq(data["seg_sr"]), unc
 
