@@ -169,6 +169,24 @@ int rehr_gather_gemm_f32(const rehr_gather_gemm_desc* d, void* stream);
  * only in lattice, taps and destination offset, in a single grid.                   */
 int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, int32_t count,
                                void* stream);
+/* The Winograd-domain weights of one call (the `count` <= 8 descriptors that rehr_gather_gemm_multi_f32 would get, scratch
+ * attached) straight from the fp32 parameter, without a panel: fills every descriptor's wino_ws with exactly what the
+ * call -- or REHR_GG_WS_ONLY -- writes there from the panel of that parameter, bit for bit; the convolution is then
+ * launched with REHR_GG_WS_READY.  No Winograd kernel dereferences wp under REHR_GG_WS_READY: it only has to pass the
+ * validation (non-null, 16-byte aligned, the same in every part).
+ *   w        the parameter in torch layout, (D0, D1, T) contiguous with T = KD * KH * KW taps: (Cout, Cin, ...) of a
+ *            Conv3d, (Cin, Cout, ...) of a ConvTranspose3d
+ *   dest_dim which of the two dimensions feeds the descriptor's destination rows (0 | 1): forward or input gradient
+ *   dest_lo, src_lo   first channel of the destination / source dimension (the halves of a virtual concat are
+ *            sub-ranges, read in place); the ranges are [dest_lo, dest_lo + Cout) and [src_lo, src_lo + Cin)
+ * The descriptor's taps select what is read, as in a launch (k0, ks, count per axis; mirrored taps, depth-tap ranges,
+ * the 2-tap phases and the 4-tap stride-2 gather of the transposed convolutions).
+ * REHR_EINVAL: what rehr_gather_gemm_multi_f32 rejects, a null or misaligned w, a range or a tap outside the parameter.
+ * REHR_ENOSUP: the launch would not run a Winograd kernel for every part (no route, no or too small a scratch, the
+ * fused kernel == stride transposed convolution): nothing is launched, the caller needs the panel. */
+int rehr_gather_gemm_wino_forms_f32(const rehr_gather_gemm_desc* descs, int32_t count, const float* w, int32_t D0,
+                                    int32_t D1, int32_t T, int32_t dest_dim, int32_t dest_lo, int32_t src_lo,
+                                    void* stream);
 /* Mixed-precision variants (BASELINE.json configs[4]: bf16 conv inputs / weights, fp32 accumulation on
  * v_mfma_f32_32x32x16_bf16, fp32 bias / fp64 statistics formed from the fp32 accumulators): the SAME descriptor
  * with x1, x2, wp and y pointing at bf16 elements (ld* and channel counts stay in ELEMENTS; rows must be

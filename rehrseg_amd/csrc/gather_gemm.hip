@@ -388,6 +388,27 @@ WinoRoute wino_route(const rehr_gather_gemm_desc& d, WinoPlan& plan) {
   return WINO_NONE;
 }
 
+// What a call of `count` parts does with the Winograd kernels, decided here for the launch and for the one-pass weight
+// forms alike.  All parts in one Winograd grid, or none: tap-range parts of a split-K launch (many depth taps; or the
+// single depth taps of a layer whose plain Winograd grid would leave half the chip idle) take the big-tile kernel, the
+// output phases of a transposed convolution on small planes the flattened-tile F(2x2,2x2) kernel.
+static WinoRoute wino_joint_route(const rehr_gather_gemm_desc* descs, int count, WinoPlan& plan) {
+  if (count > 1 && descs[0].wino_ws != nullptr) {
+    const int taps = descs[0].td.count;
+    if ((taps > 3 || taps == 1) && wino_split_plan(descs, count, plan)) return WINO_BIG8;
+    if (taps <= 3 && wino22_flat_multi_plan(descs, count, plan)) return WINO_FLAT22;
+  }
+  return WINO_NONE;
+}
+// One part on its own -- except for the tap-range parts of a split-K launch (many depth taps, few tiles): one Winograd
+// launch per part would run them one after the other on a quarter of the chip, the generic kernel runs all parts in one
+// grid.  (A scratch that is too small or misaligned is no error: the direct kernels take the descriptor.)
+static WinoRoute wino_part_route(const rehr_gather_gemm_desc& d, int count, WinoPlan& plan) {
+  if (d.wino_ws == nullptr || (count > 1 && d.td.count > 3)) return WINO_NONE;
+  const WinoRoute r = wino_route(d, plan);
+  return r != WINO_NONE && wino_ws_ok(d, plan.bytes) ? r : WINO_NONE;
+}
+
 // The weight transforms of the `count` parts that share the launch, then the launch.  REHR_GG_WS_ONLY ends here, right
 // behind the transforms, for every kernel of the family.
 static int wino_run(WinoRoute r, const rehr_gather_gemm_desc* ds, int count, const WinoPlan& plan, hipStream_t st) {
@@ -418,31 +439,18 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
   // the stride phases of a kernel == stride transposed convolution: one fused launch
   if (route[0].kind == DIRECT_TCONV_KS && !ws_only) return tconv_ks_launch(descs, count, false, st);
   WinoPlan plan{};
-  if (count > 1 && descs[0].wino_ws != nullptr) {
-    // All parts in one Winograd grid, or none.  Tap-range parts of a split-K launch (many depth taps; or the single
-    // depth taps of a layer whose plain Winograd grid would leave half the chip idle): the big-tile kernel.  Output
-    // phases of a transposed convolution on small planes: the flattened-tile F(2x2,2x2) kernel.
-    const int taps = descs[0].td.count;
-    if ((taps > 3 || taps == 1) && wino_split_plan(descs, count, plan)) return wino_run(WINO_BIG8, descs, count, plan, st);
-    if (taps <= 3 && wino22_flat_multi_plan(descs, count, plan)) return wino_run(WINO_FLAT22, descs, count, plan, st);
-  }
+  if (const WinoRoute joint = wino_joint_route(descs, count, plan)) return wino_run(joint, descs, count, plan, st);
   GGMulti pm;
   pm.interleave = 0;
   pm.count = 0;
   pm.no_interleave = (descs[0].debug_flags & REHR_DBG_GG_INTERLEAVE) ? 0 : 1;
   int n = 0;
   for (int i = 0; i < count; ++i) {
-    // fewer multiplications beat better tiling: Winograd first -- except for the tap-range parts of a split-K
-    // launch (many depth taps, few tiles): one Winograd launch per part would run them one after the other on a
-    // quarter of the chip, the generic kernel runs all parts in one grid
-    if (descs[i].wino_ws != nullptr && !(count > 1 && descs[i].td.count > 3)) {
-      const WinoRoute r = wino_route(descs[i], plan);
-      // (a scratch that is too small or misaligned is no error: the direct kernels below take the descriptor)
-      if (r != WINO_NONE && wino_ws_ok(descs[i], plan.bytes)) {
-        const int wrc = wino_run(r, &descs[i], 1, plan, st);
-        if (wrc != REHR_OK) return wrc;
-        continue;
-      }
+    // fewer multiplications beat better tiling: Winograd first (wino_part_route)
+    if (const WinoRoute r = wino_part_route(descs[i], count, plan)) {
+      const int wrc = wino_run(r, &descs[i], 1, plan, st);
+      if (wrc != REHR_OK) return wrc;
+      continue;
     }
     if (ws_only) continue;
     if (route[i].kind == DIRECT_HALO) {  // the halo-tile kernel takes what it is good at, one launch each
@@ -456,6 +464,45 @@ extern "C" int rehr_gather_gemm_multi_f32(const rehr_gather_gemm_desc* descs, in
   }
   if (n == 0) return REHR_OK;
   return launch_generic(pm, n, st);
+}
+
+extern "C" int rehr_gather_gemm_wino_forms_f32(const rehr_gather_gemm_desc* descs, int32_t count, const float* w,
+                                               int32_t D0, int32_t D1, int32_t T, int32_t dest_dim, int32_t dest_lo,
+                                               int32_t src_lo, void* stream) {
+  if (w == nullptr || ((uintptr_t)w & 3) || D0 < 1 || D1 < 1 || T < 1 || (dest_dim != 0 && dest_dim != 1) || dest_lo < 0 ||
+      src_lo < 0)
+    return REHR_EINVAL;
+  DirectRoute route[MAX_PHASES];
+  const int rrc = direct_route(descs, count, 4, route);   // validates every part, as the launch does
+  if (rrc != REHR_OK) return rrc;
+  const int Ddest = dest_dim == 0 ? D0 : D1, Dsrc = dest_dim == 0 ? D1 : D0;
+  for (int i = 0; i < count; ++i) {
+    const rehr_gather_gemm_desc& d = descs[i];
+    // the channel ranges and every tap the descriptor names lie inside the parameter
+    if (d.Cout > Ddest - dest_lo || d.Cin > Dsrc - src_lo) return REHR_EINVAL;
+    if (d.KH < 1 || d.KW < 1 || T % (d.KH * d.KW)) return REHR_EINVAL;
+    const rehr_axis_taps* ax[3] = {&d.td, &d.th, &d.tw};
+    const int ext[3] = {T / (d.KH * d.KW), d.KH, d.KW};
+    for (int a = 0; a < 3; ++a) {
+      const int64_t first = ax[a]->k0, last = (int64_t)ax[a]->k0 + (int64_t)ax[a]->ks * (ax[a]->count - 1);
+      if (first < 0 || first >= ext[a] || last < 0 || last >= ext[a]) return REHR_EINVAL;
+    }
+  }
+  // the launch would not take a Winograd kernel for every part: the caller needs the panel
+  if (route[0].kind == DIRECT_TCONV_KS) return REHR_ENOSUP;
+  WinoRoute r[MAX_PHASES];
+  WinoPlan plan{};
+  const WinoRoute joint = wino_joint_route(descs, count, plan);
+  for (int i = 0; i < count; ++i) {
+    r[i] = joint ? joint : wino_part_route(descs[i], count, plan);
+    if (r[i] == WINO_NONE) return REHR_ENOSUP;
+  }
+  WinoWeightSrc src;
+  const int64_t s0 = (int64_t)D1 * T, s1 = T;            // element strides of the parameter's two channel dimensions
+  src.sn = dest_dim == 0 ? s0 : s1;
+  src.sc = dest_dim == 0 ? s1 : s0;
+  src.w = w + dest_lo * src.sn + src_lo * src.sc;
+  return wino_forms_launch(r, descs, count, src, (hipStream_t)stream);
 }
 
 extern "C" int64_t rehr_gather_gemm_wino_bytes(const rehr_gather_gemm_desc* dp) {

@@ -65,9 +65,7 @@ __global__ void w22_weights_kernel(const rehr_gather_gemm_desc d, float* __restr
         g[a][b] = ci < d.Cin ? d.wp[(int64_t)wt * per_src + (int64_t)n * d.Cin + ci] : 0.f;
       }
     float u[9];
-    u[0] = g[0][0];              u[1] = g[0][0] + g[0][1];                     u[2] = g[0][1];
-    u[3] = g[0][0] + g[1][0];    u[4] = g[0][0] + g[0][1] + g[1][0] + g[1][1]; u[5] = g[0][1] + g[1][1];
-    u[6] = g[1][0];              u[7] = g[1][0] + g[1][1];                     u[8] = g[1][1];
+    wino_u22(g, u);
     const int nt = n >> 5, col = n & 31, chunk = ci >> 5, kk = (ci >> 3) & 3, half = (ci >> 2) & 1, e = ci & 3;
 #pragma unroll
     for (int x = 0; x < 9; ++x) {

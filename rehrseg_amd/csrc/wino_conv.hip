@@ -45,7 +45,6 @@ struct WinoParams {
 
 // U[jd][xi = r*4 + c][n][ci] = sum_{a,b} G[r][a] G[c][b] g'[a][b],  g'[dh+1][dw+1] = wp[tap with offsets (dh,dw)]
 __global__ void wino_weights_kernel(const rehr_gather_gemm_desc d, float* __restrict__ up) {
-  const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
   const int64_t per = (int64_t)d.Npad * d.Cin;
   const int64_t total = (int64_t)d.td.count * per;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -66,16 +65,10 @@ __global__ void wino_weights_kernel(const rehr_gather_gemm_desc d, float* __rest
           for (int bb = 0; bb < 3; ++bb)
             if (aa == a && bb == b) g[aa][bb] = v;
       }
-    float t[4][3];
+    float u[16];
+    wino_u33(g, u);
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) t[r][b] = G[r][0] * g[0][b] + G[r][1] * g[1][b] + G[r][2] * g[2][b];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        up[((int64_t)jd * 16 + r * 4 + c) * per + nc] = t[r][0] * G[c][0] + t[r][1] * G[c][1] + t[r][2] * G[c][2];
+    for (int xi = 0; xi < 16; ++xi) up[((int64_t)jd * 16 + xi) * per + nc] = u[xi];
   }
 }
 
@@ -311,7 +304,6 @@ constexpr int BUF2 = PW2 * RP2;        // floats per slice buffer
 // U2 in MFMA fragment order: [jd][xi][Npad/32][kchunks][kk][lane 64][4]; lane = half*32 + col
 // holds n = nt*32 + col, ci = chunk*32 + kk*8 + half*4 + e (zero beyond Cin)
 __global__ void wino_weights_frag_kernel(const rehr_gather_gemm_desc d, float* __restrict__ up, int kchunks) {
-  const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
   const int cpad = kchunks * 32;
   const int64_t per = (int64_t)d.Npad * cpad;
   const int64_t per_src = (int64_t)d.Npad * d.Cin;
@@ -336,20 +328,14 @@ __global__ void wino_weights_frag_kernel(const rehr_gather_gemm_desc d, float* _
           for (int bb = 0; bb < 3; ++bb)
             if (aa == a && bb == b) g[aa][bb] = v;
       }
-    float t[4][3];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) t[r][b] = G[r][0] * g[0][b] + G[r][1] * g[1][b] + G[r][2] * g[2][b];
+    float u[16];
+    wino_u33(g, u);
     const int nt = n >> 5, col = n & 31, chunk = ci >> 5, kk = (ci >> 3) & 3, half = (ci >> 2) & 1, e = ci & 3;
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int64_t o = (((((int64_t)jd * 16 + r * 4 + c) * NT + nt) * kchunks + chunk) * 4 + kk) * 256 +
-                          (half * 32 + col) * 4 + e;
-        up[o] = t[r][0] * G[c][0] + t[r][1] * G[c][1] + t[r][2] * G[c][2];
-      }
+    for (int xi = 0; xi < 16; ++xi) {
+      const int64_t o = (((((int64_t)jd * 16 + xi) * NT + nt) * kchunks + chunk) * 4 + kk) * 256 + (half * 32 + col) * 4 + e;
+      up[o] = u[xi];
+    }
   }
 }
 

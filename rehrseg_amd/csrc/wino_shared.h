@@ -175,6 +175,28 @@ inline bool gg_same_layer(const rehr_gather_gemm_desc& d, const rehr_gather_gemm
   return true;
 }
 
+// The transform arithmetic of the weight forms, one copy: the panel transforms (wino_weights*_kernel, w22_weights_kernel)
+// and the one-pass form kernel (wino_forms.hip) call these, so both write the same bits.
+// F(2x2,3x3): u[r*4 + c] = (G g G^T)[r][c]
+__device__ __forceinline__ void wino_u33(const float (&g)[3][3], float (&u)[16]) {
+  const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
+  float t[4][3];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) t[r][b] = G[r][0] * g[0][b] + G[r][1] * g[1][b] + G[r][2] * g[2][b];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) u[r * 4 + c] = t[r][0] * G[c][0] + t[r][1] * G[c][1] + t[r][2] * G[c][2];
+}
+// F(2x2,2x2): G = [[1,0],[1,1],[0,1]]
+__device__ __forceinline__ void wino_u22(const float (&g)[2][2], float (&u)[9]) {
+  u[0] = g[0][0];              u[1] = g[0][0] + g[0][1];                     u[2] = g[0][1];
+  u[3] = g[0][0] + g[1][0];    u[4] = g[0][0] + g[0][1] + g[1][0] + g[1][1]; u[5] = g[0][1] + g[1][1];
+  u[6] = g[1][0];              u[7] = g[1][0] + g[1][1];                     u[8] = g[1][1];
+}
+
 // One weight-transform launch: `total` items on blocks of 256 threads, at most `cap` blocks (grid-stride kernels);
 // skipped when the caller kept the transformed weights of an earlier call (REHR_GG_WS_READY).  The REHR_GG_WS_ONLY
 // return is the dispatcher's, right behind this.  (static: rehr_launch_failed is per translation unit)
@@ -205,3 +227,13 @@ bool wino22_region_plan(const rehr_gather_gemm_desc& d, WinoPlan& plan);
 bool wino22_flat_multi_plan(const rehr_gather_gemm_desc* ds, int count, WinoPlan& plan);
 int wino22_weights_launch(const rehr_gather_gemm_desc& d, const WinoPlan& plan, hipStream_t stream);
 int wino22_launch(WinoRoute r, const rehr_gather_gemm_desc* ds, int count, const WinoPlan& plan, hipStream_t stream);
+
+// wino_forms.hip: the transform-domain weights of `count` parts (route r[i], scratch attached and admitted) straight
+// from the fp32 parameter in torch layout -- no panel.  Element (tap t, destination row n, source channel ci) of the
+// parameter is w[n * sn + ci * sc + t]; rows >= d.Cout and channels >= d.Cin are zero, as in a panel.
+struct WinoWeightSrc {
+  const float* w;
+  int64_t sn, sc;
+};
+int wino_forms_launch(const WinoRoute* r, const rehr_gather_gemm_desc* ds, int count, const WinoWeightSrc& src,
+                      hipStream_t stream);

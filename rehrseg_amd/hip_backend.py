@@ -289,6 +289,67 @@ def pack_weights(w, A, Apad, B, T, transpose, dtype=torch.float32, part=None):
     return f.out
 
 
+# Trainable weights in a recorded pass (forms not kept): the fp32 Winograd kernels read only the transform-domain
+# fragments, so the panel would be written to be read once.  ops._pack gets a _LazyPanel for them; gather_gemm /
+# gather_gemm_multi fill the scratch of the call straight from the parameter (rehr_gather_gemm_wino_forms_f32: one pass,
+# the halves of a virtual concat read in place) and launch with REHR_GG_WS_READY.  The panel is packed only when the
+# library says that the launch would not run a Winograd kernel for every part (REHR_ENOSUP: the same decision as the
+# launch's, joint plans of the parts and the fused transposed-convolution kernel included) or no scratch is wanted.
+USE_ONEPASS_FORMS = True     # False: pack, then transform (tests and the A/B compare the two; the bits are the same)
+onepass_form_calls = 0       # calls whose forms came straight from the parameter (tests look at this)
+
+
+class _LazyPanel:
+    """The arguments of pack_weights for a parameter whose panel may never be needed."""
+    __slots__ = ("w", "A", "Apad", "B", "T", "transpose", "part", "_out")
+
+    def __init__(self, w, A, Apad, B, T, transpose, part):
+        self.w, self.A, self.Apad, self.B, self.T, self.transpose, self.part = w, A, Apad, B, T, bool(transpose), part
+        self._out = None
+
+    def panel(self):
+        if self._out is None:
+            self._out = pack_weights(self.w, self.A, self.Apad, self.B, self.T, self.transpose, part=self.part)
+        return self._out
+
+
+def lazy_weights(w, A, Apad, B, T, transpose, part=None):
+    """pack_weights for the fp32 gather-GEMM calls of ops: the panel itself, or -- for weights whose forms are not
+    kept -- a _LazyPanel that gather_gemm / gather_gemm_multi resolve."""
+    _chk_dev(w)
+    if (not USE_ONEPASS_FORMS or not USE_WINOGRAD or _keeps_forms(w) or w.dtype != torch.float32 or w.dim() != 5 or
+            not w.is_contiguous()):
+        return pack_weights(w, A, Apad, B, T, transpose, part=part)
+    return _LazyPanel(w, A, Apad, B, T, transpose, part)
+
+
+def _onepass_forms(arr, n, needs, lazy):
+    """Scratch for every descriptor of the call, filled from the parameter.  Returns (what must stay referenced, True)
+    when the call can run with REHR_GG_WS_READY; (the same, False) when the library wants the panel -- the scratch stays
+    attached for the transforms of the launch; None when some descriptor wants no scratch (nothing attached)."""
+    global onepass_form_calls
+    if not all(needs) or any(arr[i].Cout != lazy.A or arr[i].Cin != lazy.B for i in range(n)):
+        return None
+    w = lazy.w
+    keep = _attach_ws(arr, n, needs, None, w)       # (w is no kept panel: fresh scratch, counted as a Winograd launch)
+    dest_dim = 1 if lazy.transpose else 0
+    dest_lo = src_lo = 0
+    if lazy.part is not None:
+        if lazy.part[0] == dest_dim:
+            dest_lo = lazy.part[1]
+        else:
+            src_lo = lazy.part[1]
+    rc = L.load().rehr_gather_gemm_wino_forms_f32(arr, n, _ptr(w), w.shape[0], w.shape[1], lazy.T, dest_dim, dest_lo,
+                                                  src_lo, _stream())
+    if rc == -2:                                    # REHR_ENOSUP: some part needs the panel
+        return keep, False
+    L.check(rc, "rehr_gather_gemm_wino_forms_f32")
+    for i in range(n):
+        arr[i].flags |= L.GG_WS_READY
+    onepass_form_calls += 1
+    return keep, True
+
+
 # Kernel selection travels in the descriptors (the library reads no environment).  With `flags` / `debug_flags` = 0
 # the library picks its measured-best kernels: forward / input gradient take the Winograd kernels when the descriptor
 # carries scratch.  The switches below set `debug_flags` bits (unstable, include/rehrseg_hip.h): tests flip them to
@@ -404,6 +465,18 @@ def _attach_ws(descs, n, needs, sigs, wp):
     return f.out
 
 
+def _lazy_ws(arr, n, needs, lazy):
+    """The scratch of a call whose weights came as a _LazyPanel: forms straight from the parameter where every part
+    runs a Winograd kernel, else the panel (packed now) and the transforms of the launch."""
+    got = _onepass_forms(arr, n, needs, lazy)
+    if got is not None and got[1]:
+        return got[0]
+    panel = lazy.panel()
+    _set_panel(arr, n, panel)
+    keep = got[0] if got is not None else _attach_ws(arr, n, needs, None, panel)
+    return (keep, panel)
+
+
 def _gg_tag(arr, n=1, bf16=False):
     """Shape of the call and, in brackets, the kernel the library runs for it: the Winograd route of a descriptor that
     carries scratch, else the direct kernel(s) of the parts.  Evaluated by _timed only while a profile is running."""
@@ -457,7 +530,21 @@ def _gg_family(d):
     return "wino22_conv" if route in (L.GG_ROUTE_FLAT22, L.GG_ROUTE_REGION22) else "wino_conv"
 
 
+def _with_wp(args, wp):
+    return args[:11] + (wp,) + args[12:]
+
+
+def _set_panel(arr, n, panel):
+    for i in range(n):
+        arr[i].wp = _ptr(panel)
+
+
 def gather_gemm(*args):
+    lazy = args[11] if isinstance(args[11], _LazyPanel) else None
+    if lazy is not None:
+        # the descriptor is planned with the parameter standing in for the panel (wp only has to pass the validation;
+        # a parameter that is not 16-byte aligned gets no Winograd scratch and takes the panel path below)
+        args = _with_wp(args, lazy.w)
     d = L.GatherGemmDesc()
     flops = _gg_desc(d, *args)
     if args[0].dtype == torch.bfloat16:
@@ -465,7 +552,8 @@ def gather_gemm(*args):
             L.check(L.load().rehr_gather_gemm_bf16(C.byref(d), _stream()), "rehr_gather_gemm_bf16")
         return
     arr = (L.GatherGemmDesc * 1)(d)
-    keep = _attach_ws(arr, 1, [_gg_desc.need], [_gg_desc.sig], args[11])
+    keep = _lazy_ws(arr, 1, [_gg_desc.need], lazy) if lazy is not None else \
+        _attach_ws(arr, 1, [_gg_desc.need], [_gg_desc.sig], args[11])
     with _timed(_gg_family(arr[0]), flops, lambda: _gg_tag(arr)):
         L.check(L.load().rehr_gather_gemm_multi_f32(arr, 1, _stream()), "rehr_gather_gemm_f32")
     del keep
@@ -475,6 +563,9 @@ def gather_gemm_multi(calls):
     """`calls` = argument tuples of gather_gemm for the stride phases of one layer: one grid."""
     if len(calls) == 1:
         return gather_gemm(*calls[0])
+    lazy = calls[0][11] if isinstance(calls[0][11], _LazyPanel) else None
+    if lazy is not None:
+        calls = [_with_wp(a, lazy.w) for a in calls]      # (the parameter stands in for the panel: see gather_gemm)
     arr = (L.GatherGemmDesc * len(calls))()
     flops, needs, sigs = 0.0, [], []
     for i, a in enumerate(calls):
@@ -485,7 +576,8 @@ def gather_gemm_multi(calls):
         with _timed("gather_gemm_bf16", flops, lambda: f"{len(calls)} parts of " + _gg_tag(arr, len(calls), bf16=True)):
             L.check(L.load().rehr_gather_gemm_multi_bf16(arr, len(calls), _stream()), "rehr_gather_gemm_multi_bf16")
         return
-    keep = _attach_ws(arr, len(calls), needs, sigs, calls[0][11])   # every part its own scratch: ONE launch runs them all
+    keep = _lazy_ws(arr, len(calls), needs, lazy) if lazy is not None else \
+        _attach_ws(arr, len(calls), needs, sigs, calls[0][11])   # every part its own scratch: ONE launch runs them all
     with _timed(_gg_family(arr[0]) if all(arr[i].wino_ws for i in range(len(calls))) else "gather_gemm", flops,
                 lambda: f"{len(calls)} parts of " + _gg_tag(arr, len(calls))):
         L.check(L.load().rehr_gather_gemm_multi_f32(arr, len(calls), _stream()), "rehr_gather_gemm_multi_f32")

@@ -129,6 +129,7 @@ PROTOTYPES = {
     "rehr_gather_gemm_direct_route": (C.c_int, [_P_GG, _i32, _i32, C.POINTER(_i32)]),
     "rehr_gather_gemm_f32": (C.c_int, [_P_GG, _vp]),
     "rehr_gather_gemm_multi_f32": (C.c_int, [_P_GG, _i32, _vp]),
+    "rehr_gather_gemm_wino_forms_f32": (C.c_int, [_P_GG, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "rehr_gather_gemm_bf16": (C.c_int, [_P_GG, _vp]),
     "rehr_gather_gemm_multi_bf16": (C.c_int, [_P_GG, _i32, _vp]),
     "rehr_pack_weights_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

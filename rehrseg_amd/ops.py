@@ -188,11 +188,13 @@ def _pack(w, dest_dim, dtype=torch.float32, part=None):
         else:
             w = w.narrow(*part).contiguous()
         shape[part[0]] = part[2]
+    # fp32 on the HIP backend: the panel may never be needed (lazy_weights; the gather-GEMM calls resolve what they get)
+    pack = getattr(be, "lazy_weights", be.pack_weights) if dtype != torch.bfloat16 else be.pack_weights
     if dest_dim == 0:
         A, B = shape[0], shape[1]
-        return be.pack_weights(w, A, pad_rows(A), B, T, False, **kw), pad_rows(A)
+        return pack(w, A, pad_rows(A), B, T, False, **kw), pad_rows(A)
     A, B = shape[1], shape[0]
-    return be.pack_weights(w, A, pad_rows(A), B, T, True, **kw), pad_rows(A)
+    return pack(w, A, pad_rows(A), B, T, True, **kw), pad_rows(A)
 
 
 def _phased_gather(src1, src2, c1, Csrc, wp, Npad, dst, Cdst, K, stride, pad, bias, act, slope, stats, stats_mode):
