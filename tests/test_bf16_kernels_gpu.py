@@ -1,11 +1,15 @@
 """Mixed-precision kernels (BASELINE.json configs[4]: bf16 operands, fp32 accumulate) against torch.nn.functional
 in fp64 evaluated on the SAME bf16-rounded inputs and weights.  Tolerance: what is left is the fp32 accumulation
-order and the final rounding of the output to bf16 (2^-9 relative per element) -> 1e-2 of the tensor's max for
-bf16 outputs, 1e-4 for fp32 outputs / statistics / weight gradients."""
+order and the final rounding of the output to bf16.  A bf16 output that has passed that ONE rounding (y, dx of the
+convolution entry points) is held element by element to |got - ref| <= 2^-8 |ref| + 1e-4 max|ref| and the conv-epilogue
+statistics to 5e-6 of the sum of |summand| per (sample, channel) (tests/bf16_bar.py, where both are derived; edge
+shapes: tests/test_bf16_conv_edges_gpu.py); 1e-4 of the tensor's max for fp32 outputs / weight gradients.  Two bf16
+results compared with EACH OTHER (the halo-against-gather cross-check) keep 1e-2 of the max: two roundings."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+from bf16_bar import assert_bf16_bar, assert_conv_stats
 from rehrseg_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -45,15 +49,15 @@ def test_conv3d_forward_and_input_gradient_bf16(case):
     assert y.dtype == BF and y.shape[1] == Cout
     wq = w.to(BF).double()
     ref = F.leaky_relu(F.conv3d(x.double(), wq, b.double(), s, p), 0.1)
-    assert relmax(y, ref) < 1e-2
+    assert_bf16_bar(f"{case} y", y, ref)
     # statistics come from the fp32 accumulators (before the bf16 rounding of y)
-    assert relmax(stats[..., 0], ref.sum((2, 3, 4))) < 2e-3 and relmax(stats[..., 1], (ref ** 2).sum((2, 3, 4))) < 1e-3
+    assert_conv_stats(f"{case} stats", stats, ref)
     dz = act(tuple(ref.shape), g)
     dx, _ = ops.conv_dgrad(dz, w, (D, H, W), Cin, 0, cfg)
     assert dx.dtype == BF
     xr = x.double().requires_grad_()
     F.conv3d(xr, wq, None, s, p).backward(dz.double())
-    assert relmax(dx, xr.grad) < 1e-2
+    assert_bf16_bar(f"{case} dx", dx, xr.grad)
 
 
 def test_virtual_concat_and_fp32_output_bf16():
@@ -63,12 +67,13 @@ def test_virtual_concat_and_fp32_output_bf16():
     cfg = ops.ConvCfg((1, 1, 1), (1, 1, 1))
     y, _ = ops.conv_forward(x1, x2, w, None, cfg, ops.ACT_NONE, 0.0, 0)
     ref = F.conv3d(torch.cat([x1, x2], 1).double(), w.to(BF).double(), None, 1, 1)
-    assert relmax(y, ref) < 1e-2
+    assert_bf16_bar("virtual concat y", y, ref)
     dz = act(tuple(ref.shape), g)
     d1, d2 = ops.conv_dgrad(dz, w, (4, 12, 12), 64, 32, cfg)
     xr = torch.cat([x1, x2], 1).double().requires_grad_()
     F.conv3d(xr, w.to(BF).double(), None, 1, 1).backward(dz.double())
-    assert relmax(d1, xr.grad[:, :64]) < 1e-2 and relmax(d2, xr.grad[:, 64:]) < 1e-2
+    assert_bf16_bar("virtual concat dx1", d1, xr.grad[:, :64])
+    assert_bf16_bar("virtual concat dx2", d2, xr.grad[:, 64:])
 
 
 @pytest.mark.parametrize("K,s,p", [((2, 2, 2), (2, 2, 2), (0, 0, 0)), ((1, 2, 2), (1, 2, 2), (0, 0, 0)),
@@ -81,12 +86,13 @@ def test_conv_transpose3d_bf16(K, s, p):
     cfg = ops.ConvCfg(s, p, transposed=True)
     y, _ = ops.conv_forward(x, None, w, b, cfg, ops.ACT_NONE, 0.0, 0)
     ref = F.conv_transpose3d(x.double(), w.to(BF).double(), b.double(), s, p)
-    assert tuple(y.shape) == tuple(ref.shape) and relmax(y, ref) < 1e-2
+    assert tuple(y.shape) == tuple(ref.shape)
+    assert_bf16_bar(f"transposed {K}/{s} y", y, ref)
     dz = act(tuple(ref.shape), g)
     dx, _ = ops.conv_dgrad(dz, w, tuple(x.shape[2:]), 128, 0, cfg)
     xr = x.double().requires_grad_()
     F.conv_transpose3d(xr, w.to(BF).double(), None, s, p).backward(dz.double())
-    assert relmax(dx, xr.grad) < 1e-2
+    assert_bf16_bar(f"transposed {K}/{s} dx", dx, xr.grad)
 
 
 WG_CASES = [  # (N, Cin, Cout, D, H, W, kernel, stride, pad, transposed)
@@ -166,8 +172,10 @@ def test_halo_brick_kernel_matches_gather_kernel_and_torch(case):
     F.conv3d(xr, wq, None, 1, p).backward(dz.double())
     for halo in (True, False):
         y, stats, dx = res[halo]
-        assert relmax(y, ref) < 1e-2 and relmax(dx, xr.grad) < 1e-2, halo
-        assert relmax(stats[..., 0], ref.sum((2, 3, 4))) < 2e-3 and relmax(stats[..., 1], (ref ** 2).sum((2, 3, 4))) < 1e-3
+        tag = f"{case} {'halo' if halo else 'gather'}"
+        assert_bf16_bar(f"{tag} y", y, ref)
+        assert_bf16_bar(f"{tag} dx", dx, xr.grad)
+        assert_conv_stats(f"{tag} stats", stats, ref)
     # the two kernels form the same fp32 sums in a different order: identical after rounding to bf16 almost everywhere
     assert relmax(res[True][0], res[False][0]) < 1e-2 and relmax(res[True][1], res[False][1]) < 1e-5
 
@@ -179,14 +187,14 @@ def test_halo_brick_kernel_virtual_concat_and_transposed_phase_taps():
     cfg = ops.ConvCfg((1, 1, 1), (1, 1, 1))
     y, _ = ops.conv_forward(x1, x2, w, None, cfg, ops.ACT_NONE, 0.0, 0)
     ref = F.conv3d(torch.cat([x1, x2], 1).double(), w.to(BF).double(), None, 1, 1)
-    assert relmax(y, ref) < 1e-2
+    assert_bf16_bar("halo virtual concat y", y, ref)
     # ConvTranspose3d (3,4,4)/(1,2,2): every output phase is a unit-stride 3x2x2-tap gather written at stride 2
     xt = act((1, 64, 4, 16, 16), g)
     wt = (torch.randn(64, 64, 3, 4, 4, generator=g) / (64 * 12) ** 0.5).to(DEV)
     ct = ops.ConvCfg((1, 2, 2), (1, 1, 1), transposed=True)
     yt, _ = ops.conv_forward(xt, None, wt, None, ct, ops.ACT_NONE, 0.0, 0)
     rt = F.conv_transpose3d(xt.double(), wt.to(BF).double(), None, (1, 2, 2), (1, 1, 1))
-    assert relmax(yt, rt) < 1e-2
+    assert_bf16_bar("transposed phase taps y", yt, rt)
 
 
 BRICK_WG_CASES = [  # shapes the LDS-brick weight-gradient kernel takes: (N, Cin, Cout, D, H, W, kernel, pad)
@@ -434,15 +442,15 @@ def test_split_k_in_mixed_precision(stats):
     y, st = ops.conv_forward(x, None, w, b, cfg, ops.ACT_NONE, 0.0, 2 if stats else 0)
     assert y.dtype == torch.bfloat16
     ref = F.conv3d(x.double().cpu(), w.to(torch.bfloat16).double().cpu(), b.double().cpu(), 1, 1)
-    assert relmax(y, ref) < 2.0 ** -7
+    assert_bf16_bar("split-K y", y, ref)
     if stats:
-        want = torch.stack([ref.sum((2, 3, 4)), (ref * ref).sum((2, 3, 4))], -1)
-        torch.testing.assert_close(st.cpu(), want, rtol=1e-4, atol=1e-3)
+        assert_conv_stats("split-K stats", st, ref)
     dz = torch.randn(1, 320, 8, 5, 5, generator=g).to(DEV).to(torch.bfloat16).contiguous(memory_format=torch.channels_last_3d)
     dx = ops.conv_dgrad(dz, w, (8, 5, 5), 320, 0, cfg)[0]
     xr = x.double().cpu().requires_grad_()
     F.conv3d(xr, w.to(torch.bfloat16).double().cpu(), None, 1, 1).backward(dz.double().cpu())
-    assert dx.dtype == torch.bfloat16 and relmax(dx, xr.grad) < 2.0 ** -7
+    assert dx.dtype == torch.bfloat16
+    assert_bf16_bar("split-K dx", dx, xr.grad)
 
 
 def test_instnorm_backward_carries_the_conv_bias_gradient():
