@@ -1357,6 +1357,62 @@ def seg_eval_finalize(logits, counts, stats, crop=None, labels=None, gt=None):
                                                 _ptr(stats), _stream()), "rehr_seg_eval_finalize_f16")
 
 
+# ----------------------------------------------------------------------------- boundary metrics (seg_surface.hip)
+SEG_SURFACE_MAX_AXIS = 2048     # REHR_SEG_SURFACE_MAX_AXIS
+SEG_SURFACE_MAX_VOXELS = 1 << 30
+
+
+def seg_surface_check_extent(shape):
+    """Raises for a (D, H, W) the surface kernels do not take; no launch, no allocation."""
+    dims = tuple(int(v) for v in shape)
+    if len(dims) != 3 or min(dims) < 1:
+        raise L.RehrsegHipError(f"surface metrics: a (D, H, W) volume with every axis >= 1, got {dims}")
+    if max(dims) > SEG_SURFACE_MAX_AXIS or dims[0] * dims[1] * dims[2] > SEG_SURFACE_MAX_VOXELS:
+        raise L.RehrsegHipError(f"surface metrics: unsupported extent {dims}: every axis <= {SEG_SURFACE_MAX_AXIS} and "
+                                f"at most 2**30 voxels (REHR_ENOSUP)")
+    return dims
+
+
+def _surface_workspace(dims, device):
+    nbytes = L.load().rehr_seg_surface_workspace_bytes(*dims)
+    if nbytes < 0:
+        L.check(int(nbytes), "rehr_seg_surface_workspace_bytes")
+    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+
+
+def seg_surface_distances(pred, gt, spacing, counts, workspace=None):
+    """pred, gt: uint8 (D, H, W), non-zero = foreground; spacing (sd, sh, sw) as fp32 values.  Returns (dist fp32
+    [2, D*H*W], workspace): dist[0] the distance of every surface voxel of pred to gt's surface, dist[1] the reverse,
+    +inf at the other voxels; counts (int64 [2], zeroed) += the two surface sizes (rehr_seg_surface_dist_f32)."""
+    _chk_eval(pred, torch.uint8, "seg_surface_distances pred", 3)
+    _chk_eval(gt, torch.uint8, "seg_surface_distances gt", 3)
+    _chk_eval(counts, torch.int64, "seg_surface_distances counts", 1)
+    dims = seg_surface_check_extent(pred.shape)
+    if tuple(gt.shape) != dims or counts.numel() != 2:
+        raise L.RehrsegHipError("seg_surface_distances: gt has pred's shape, 2 counts")
+    if workspace is None:
+        workspace = _surface_workspace(dims, pred.device)
+    dist = torch.empty((2, dims[0] * dims[1] * dims[2]), device=pred.device, dtype=torch.float32)
+    L.check(L.load().rehr_seg_surface_dist_f32(_ptr(pred), _ptr(gt), *dims, *(float(s) for s in spacing), _ptr(dist),
+                                               _ptr(counts), _ptr(workspace), workspace.numel(), _stream()),
+            "rehr_seg_surface_dist_f32")
+    return dist, workspace
+
+
+def seg_surface_reduce(dist, dist_sorted, counts, out, workspace):
+    """out (int64 [3], the bits of three fp64) = hd, hd95, assd from dist [2, N], its ascending sort [2 * N] and the
+    counts, all on the device (rehr_seg_surface_reduce_f64)."""
+    _chk_eval(dist, torch.float32, "seg_surface_reduce dist", 2)
+    _chk_eval(dist_sorted, torch.float32, "seg_surface_reduce sorted", 1)
+    _chk_eval(counts, torch.int64, "seg_surface_reduce counts", 1)
+    _chk_eval(out, torch.int64, "seg_surface_reduce out", 1)
+    if dist.shape[0] != 2 or dist_sorted.numel() != dist.numel() or counts.numel() != 2 or out.numel() != 3:
+        raise L.RehrsegHipError("seg_surface_reduce: dist [2, N], sorted [2 * N], 2 counts, 3 outputs")
+    L.check(L.load().rehr_seg_surface_reduce_f64(_ptr(dist), _ptr(dist_sorted), _ptr(counts), dist.shape[1], _ptr(out),
+                                                 _ptr(workspace), workspace.numel(), _stream()),
+            "rehr_seg_surface_reduce_f64")
+
+
 # ----------------------------------------------------------------------------- stage-1 -> stage-2 handoff (sr_volume.hip)
 def minmax_new(device, pairs=1):
     """`pairs` empty {min, max} code pairs (int32 storage of the kernels' order-preserving uint32 codes)."""

@@ -221,39 +221,71 @@ def _report(dice, terms):
     return sum(dice) / len(dice)
 
 
-def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1, *, device=None):
+def _subject_line(name, dice, surf=None):
+    if surf is None:
+        return f"Subject {name}: {dice}"
+    return f"Subject {name}: {dice} | HD95: {surf['hd95']} | ASSD: {surf['assd']}"
+
+
+def _report_surface(surf):
+    """Mean, std, max and min of HD95 and ASSD over the cases where they are finite, and the number of cases with an
+    empty surface (no foreground in the prediction or in the label: NaN)."""
+    for key, label in (("hd95", "HD95"), ("assd", "ASSD")):
+        vals = [s[key] for s in surf if np.isfinite(s[key])]
+        if vals:
+            print(f"Average {label}: {sum(vals) / len(vals)}")
+            print(f"Std {label}: {np.std(vals)}")
+            print(f"Max {label}: {max(vals)}")
+            print(f"Min {label}: {min(vals)}")
+        else:
+            print(f"Average {label}: nan (no case with both surfaces)")
+    print(f"Empty-surface cases: {sum(1 for s in surf if s['n_pred'] == 0 or s['n_gt'] == 0)} of {len(surf)}")
+
+
+def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1, *, device=None, surface=False,
+                   spacing=None):
     """train_all.py:154-193 over in-memory cases: `cases` yields (name, image, label), each a (1, D, H, W) array or
     tensor (or a file name).  Prints the reference's summary and returns the mean Dice.
 
     The global Dice is calculate_dice over the concatenated LR maps, formed from the summed per-case integer terms, so
     no map is kept.  (The reference concatenates float32 label tensors, so its float32 sums can differ from these
-    exact ones in the last bits once the counts pass 2**24.)  `device`: as evaluate_case's."""
+    exact ones in the last bits once the counts pass 2**24.)  `device`: as evaluate_case's.
+
+    With `surface=True` every subject's line gains HD95 and ASSD (evaluate_case's `surface` / `spacing`) and the
+    summary their mean, std, max and min over the cases with finite values and the number of cases with an empty
+    surface; the return value stays the mean Dice."""
     from .utils.seg_utils import _evaluate_case
-    dice, terms = [], []
+    dice, terms, surf = [], [], []
     for name, img, label in cases:
-        out = _evaluate_case(model_seg, img, label, seperation, patch_size_ori[::-1], eval_HR, device)
-        print(f"Subject {name}: {out[3]}")
+        out = _evaluate_case(model_seg, img, label, seperation, patch_size_ori[::-1], eval_HR, device, surface, spacing)
+        print(_subject_line(name, out[3], out[5] if surface else None))
         dice.append(out[3])
         terms.append(out[4])
-    return _report(dice, terms)
+        surf.extend(out[5:])
+    mean = _report(dice, terms)
+    if surface:
+        _report_surface(surf)
+    return mean
 
 
 def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path, fold, save_path=None, eval_HR=False,
-             seperation=1):
+             seperation=1, surface=False):
     """train_all.py:154-193: every validation subject of the split's fold, read with SimpleITK; with `save_path`, the
-    predictions are written next to it as NIfTI via SimpleITK as the reference does."""
+    predictions are written next to it as NIfTI via SimpleITK as the reference does.  `surface`: as evaluate_cases',
+    in the units of each image file's spacing."""
     import json
     import os
     from .utils.seg_utils import _evaluate_case, _sitk
     sitk = _sitk()
     with open(split_path, "r") as f:
         split_data = json.load(f)[fold]["val"]
-    dice, terms = [], []
+    dice, terms, surf = [], [], []
     for subject in split_data:
         test_img = os.path.join(val_img_path, subject + "_0000.nii.gz")
         test_label = os.path.join(val_label_path, subject + ".nii.gz")
-        pred_lr, pred_hr, _, dice_lr, t = _evaluate_case(model_seg, test_img, test_label, seperation,
-                                                          patch_size_ori[::-1], eval_HR)
+        pred_lr, pred_hr, _, dice_lr, t, *s = _evaluate_case(model_seg, test_img, test_label, seperation,
+                                                              patch_size_ori[::-1], eval_HR, None, surface)
+        surf.extend(s)
         if save_path is not None:
             os.makedirs(os.path.join(save_path, "val"), exist_ok=True)
             ori = sitk.ReadImage(test_img)
@@ -269,7 +301,10 @@ def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path
                 img.SetOrigin(ori.GetOrigin())
                 img.SetDirection(ori.GetDirection())
                 sitk.WriteImage(img, os.path.join(save_path, "val", f"{subject}_pred_hr.nii.gz"))
-        print(f"Subject {subject}: {dice_lr}")
+        print(_subject_line(subject, dice_lr, s[0] if surface else None))
         dice.append(dice_lr)
         terms.append(t)
-    return _report(dice, terms)
+    mean = _report(dice, terms)
+    if surface:
+        _report_surface(surf)
+    return mean

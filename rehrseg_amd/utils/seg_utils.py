@@ -632,28 +632,116 @@ def _model_device(model):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, device=None):
-    """evaluate_case, plus the exact Dice terms (intersection, sum of the prediction, sum of the label)."""
+# ----------------------------------------------------------------------------- boundary metrics
+def _spacing_f32(spacing):
+    """(sd, sh, sw) in the array's axis order, rounded once to fp32: the values the kernels use, as Python floats."""
+    sp = np.asarray(spacing, dtype=np.float64).reshape(-1)
+    if sp.shape != (3,):
+        raise ValueError(f"spacing must have 3 entries (sd, sh, sw), got {spacing!r}")
+    sp = sp.astype(np.float32)
+    if not (np.isfinite(sp).all() and (sp > 0).all()):
+        raise ValueError(f"spacing must be finite and positive, got {spacing!r}")
+    return tuple(float(v) for v in sp)
+
+
+def _surface_launch(be, pred, gt, spacing, out):
+    """The surface kernels on two uint8 maps on the device; out (int64 [5], zeroed) receives the bits of the fp64
+    hd, hd95, assd and the two surface sizes.  No host sync; the sort between the two calls is torch's."""
+    counts = out[3:5]
+    dist, workspace = be.seg_surface_distances(pred, gt, spacing, counts)
+    be.seg_surface_reduce(dist, torch.sort(dist.view(-1)).values, counts, out[0:3], workspace)
+
+
+def _surface_result(vals):
+    """The host form of _surface_launch's five int64."""
+    vals = np.ascontiguousarray(np.asarray(vals, dtype=np.int64))
+    hd, hd95, assd = (float(v) for v in vals[:3].view(np.float64))
+    return {"hd": hd, "hd95": hd95, "assd": assd, "n_pred": int(vals[3]), "n_gt": int(vals[4])}
+
+
+def _map_shape(a):
+    shape = tuple(int(n) for n in a.shape)
+    if len(shape) == 4 and shape[0] == 1:
+        shape = shape[1:]
+    if len(shape) != 3:
+        raise ValueError(f"expected a (D, H, W) or (1, D, H, W) label map, got {tuple(a.shape)}")
+    return shape
+
+
+def _binary_u8(a, dev):
+    """A (D, H, W) or (1, D, H, W) array or tensor of any dtype -> its non-zero mask as uint8 (D, H, W) on dev."""
+    if isinstance(a, torch.Tensor):
+        t = a.detach()
+        if t.device != dev:
+            t = t.to(dev) if t.is_cuda else _upload(t.contiguous(), dev)
+        t = (t != 0).to(torch.uint8)
+    else:
+        t = _upload(torch.from_numpy((np.asarray(a) != 0).astype(np.uint8)), dev)
+    return t.reshape(_map_shape(a)).contiguous()
+
+
+def surface_distance_metrics(prediction, ground_truth, spacing=(1., 1., 1.), *, device=None):
+    """Boundary metrics of two label maps in the units of `spacing`: {'hd', 'hd95', 'assd'} as floats and
+    {'n_pred', 'n_gt'}, the sizes of the two surfaces, as ints.
+
+    `prediction` / `ground_truth`: (D, H, W) or (1, D, H, W) numpy arrays or tensors of any integer, bool or float
+    dtype, on the host or on the device; non-zero is foreground.  `spacing` = (sd, sh, sw) in the array's axis order
+    (read_image's properties['spacing'] has it), converted to fp32 once.  A surface voxel is a foreground voxel with a
+    background face neighbour (outside the volume is background); hd is the largest distance of a surface voxel of one
+    map to the surface of the other, hd95 numpy.percentile(., 95) of all those distances, assd the mean of the two
+    directed means.  All three are NaN when either map has no foreground (the counts say which).  Everything runs on
+    the device (csrc/seg_surface.hip); the call makes one host sync, the read of the five numbers.  Raises
+    RehrsegHipError for an axis above 2048 or more than 2**30 voxels.  `device` defaults to a device tensor's, else
+    the current device."""
+    from .. import ops
+    from ..hip_backend import seg_surface_check_extent
+    be = ops.get_backend()
+    sp = _spacing_f32(spacing)
+    shape = _map_shape(prediction)
+    if _map_shape(ground_truth) != shape:
+        raise ValueError(f"prediction {shape} and ground truth {_map_shape(ground_truth)} differ in shape")
+    seg_surface_check_extent(shape)     # before any upload or launch
+    if device is not None:
+        dev = torch.device(device)
+    else:
+        on_dev = [a.device for a in (prediction, ground_truth) if isinstance(a, torch.Tensor) and a.is_cuda]
+        dev = on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
+    pred, gt = _binary_u8(prediction, dev), _binary_u8(ground_truth, dev)
+    out = torch.zeros(5, dtype=torch.int64, device=dev)
+    _surface_launch(be, pred, gt, sp, out)
+    return _surface_result(out.cpu().numpy())   # the one host sync
+
+
+def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, device=None,
+                   surface=False, spacing=None):
+    """evaluate_case, plus the exact Dice terms (intersection, sum of the prediction, sum of the label) and, with
+    `surface`, the boundary metrics of the LR maps as a sixth element."""
     from .. import ops
     be = ops.get_backend()
     model.eval()
     sep = _integral_separation(slice_separation)
     dev = torch.device(device) if device is not None else _model_device(model)
-    lr_data, _ = preprocess_image(case_img)
+    lr_data, properties = preprocess_image(case_img)
     lr_label, _ = preprocess_image(case_label, apply_norm=False)
+    if surface:
+        sp = _spacing_f32(spacing if spacing is not None else properties.get("spacing", (1., 1., 1.)))
     patch = [int(p) for p in patch_size]
     padded, pad, _ = _pad_geometry(lr_data.shape[1:], patch)
     revert = tuple(slice(b, b + n) for b, n in zip(pad, lr_data.shape[1:]))
     vol = _upload(lr_data[0], dev)
     gt = _upload(torch.from_numpy(lr_label.squeeze(0).numpy().astype("uint8")), dev)
     slicers = _internal_get_sliding_window_slicers(padded, patch_size=patch)
-    stats = torch.zeros((2, 4), dtype=torch.int64, device=dev)
+    # with `surface`, the five numbers of the boundary metrics ride behind the eight stats in the same tensor
+    buf = torch.zeros(13 if surface else 8, dtype=torch.int64, device=dev)
+    stats = buf[:8].view(2, 4)
     with torch.no_grad():
         logits, counts = _fused_tiles(vol, pad, slicers, model, 0, False, 1, _device_gaussian(tuple(patch), str(dev)))
         labels_lr = torch.empty(tuple(gt.shape), dtype=torch.uint8, device=dev)
         be.seg_eval_finalize(logits, counts, stats[0], revert, labels_lr, gt)
         del logits, counts
         lr_host = _to_host(labels_lr)
+        if surface:
+            _surface_launch(be, labels_lr, gt, sp, buf[8:])
         if get_HR_results:
             # the reference's HR branch: no Gaussian, no softmax, and the padding is not reverted
             logits, counts = _fused_tiles(vol, pad, slicers, model, 1, True, sep, None)
@@ -661,15 +749,18 @@ def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, ge
             be.seg_eval_finalize(logits, counts, stats[1], None, labels_hr)
             del logits, counts
             hr_host = _to_host(labels_hr)
-    st = stats.cpu().numpy()  # the one host sync of the case: after it the label maps are on the host as well
+    host = buf.cpu().numpy()  # the one host sync of the case: after it the label maps are on the host as well
+    st = host[:8].reshape(2, 4)
     _check_inf(st[0, 0] or st[1, 0])
     prediction_lr = lr_host.numpy()
     prediction_hr = hr_host.numpy() if get_HR_results else prediction_lr
     terms = tuple(int(v) for v in st[0, 1:])
-    return prediction_lr, prediction_hr, lr_label, _dice_from_counts(*terms), terms
+    out = (prediction_lr, prediction_hr, lr_label, _dice_from_counts(*terms), terms)
+    return out + (_surface_result(host[8:]),) if surface else out
 
 
-def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, *, device=None):
+def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, *, device=None,
+                  surface=False, spacing=None):
     """ref :736-784 on the device: (prediction_lr uint8 (D, H, W), prediction_hr, lr_label float (1, D, H, W) CPU
     tensor, dice_lr float64).
 
@@ -682,5 +773,12 @@ def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get
     torch.autocast fp16 region has no effect on the HIP kernels and is not opened.  The argmax is taken on the fp16
     logits instead of their fp32 softmax: the same class except for two logits within one fp16 ulp of each other,
     where exp rounding can make the softmax tie.  `slice_separation` must be integral (ValueError otherwise).
-    `device` defaults to the model's."""
-    return _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results, device)[:4]
+    `device` defaults to the model's.
+
+    With `surface=True` a fifth element follows: surface_distance_metrics' dict for the LR prediction against the LR
+    label, in the units of `spacing` = (sd, sh, sw), else of the image file's properties['spacing'], else (1, 1, 1).
+    The surface kernels run on the two maps while they are on the device and their results travel with the same
+    read: still one host sync.  With `surface=False` nothing changes."""
+    out = _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results, device, surface,
+                         spacing)
+    return out[:4] + out[5:]
