@@ -731,6 +731,34 @@ int rehr_seg_surface_reduce_f64(const float* dist, const float* sorted, const ui
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Stage-2 validation, connected components and lesion-wise scores (csrc/seg_components.hip).  A mask is
+ * uint8 (D, H, W), contiguous, non-zero = foreground; connectivity 6, 18 or 26 = face, + edge, + corner neighbours
+ * (scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3)); outside the volume is background and nothing wraps around
+ * a row or a slice.  Every axis >= 1 and D * H * W <= 2^30, anything else REHR_ENOSUP; a null pointer, another
+ * connectivity, a misaligned or too small workspace: REHR_EINVAL; all before any launch.  Every call is a fixed number
+ * of launches and reads nothing back.
+ * ------------------------------------------------------------------------- */
+/* Bytes of the workspace of the two calls below (64 + 16 per voxel), or the error code. */
+int64_t rehr_seg_cc_workspace_bytes(int32_t D, int32_t H, int32_t W);
+/* roots[v] = the smallest linear index (d * H + h) * W + w of any voxel of v's component, -1 at a background voxel:
+ * a function of the mask alone, the same bits on every run.  The workspace is checked and not written. */
+int rehr_seg_cc_roots_i32(const uint8_t* mask, int32_t D, int32_t H, int32_t W, int32_t connectivity, int32_t* roots,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+/* out: int64[8], zeroed by the caller, each slot added to: [0] n_pred and [1] n_gt, the numbers of components;
+ * [2] tp_pred, predicted components with at least one foreground voxel of gt; [3] tp_gt, the reverse; [4], [5] the
+ * voxels of the largest component of pred / gt (among equal sizes the one with the smaller root); [6] the foreground
+ * voxels of gt inside that largest component of pred; [7] the foreground voxels of gt.  roots_*: as written above, N
+ * words each (a word outside [0, N) counts as background).  workspace: 16-byte aligned, at least 64 + 16 N bytes,
+ * overwritten; on return its first two uint64 are the keys (size << 32) | (0xffffffff - root) of the largest
+ * component of pred and of gt, 0 for an empty map. */
+int rehr_seg_cc_lesion_i64(const int32_t* roots_pred, const int32_t* roots_gt, int64_t N, int64_t* out,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+/* labels[v] = rank[roots[v]], 0 at background, where rank is the inclusive prefix sum over v of (roots[v] == v) as
+ * int32 (the caller's scan): 1..n in the order of the roots.  count: int64[1], zeroed by the caller, += n. */
+int rehr_seg_cc_compact_i32(const int32_t* roots, int64_t N, const int32_t* rank, int32_t* labels, int64_t* count,
+                            void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Stage-1 -> stage-2 volume handoff on the device (utils/sr_utils.py:137-242 inference_flavr, :279-304 zeroonenorm /
  * postprocess_flavr; rehrseg_amd/utils/sr_utils.py drives them, csrc/sr_volume.hip).
  * A "minmax" buffer is two uint32 codes {min, max} that order like the floats they stand for:

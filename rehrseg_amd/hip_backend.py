@@ -1413,6 +1413,83 @@ def seg_surface_reduce(dist, dist_sorted, counts, out, workspace):
             "rehr_seg_surface_reduce_f64")
 
 
+# ----------------------------------------------------------------------------- connected components (seg_components.hip)
+SEG_CC_MAX_VOXELS = 1 << 30
+SEG_CC_CONNECTIVITIES = (6, 18, 26)
+
+
+def seg_cc_check_extent(shape):
+    """Raises for a (D, H, W) the component kernels do not take; no launch, no allocation."""
+    dims = tuple(int(v) for v in shape)
+    if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] > SEG_CC_MAX_VOXELS:
+        raise L.RehrsegHipError(f"connected components: unsupported extent {dims}: a (D, H, W) volume with every "
+                                f"axis >= 1 and at most 2**30 voxels (REHR_ENOSUP)")
+    return dims
+
+
+def _cc_connectivity(connectivity):
+    if connectivity not in SEG_CC_CONNECTIVITIES:
+        raise L.RehrsegHipError(f"connected components: connectivity 6, 18 or 26, got {connectivity!r}")
+    return int(connectivity)
+
+
+def seg_cc_workspace(dims, device):
+    """The workspace of seg_cc_roots / seg_cc_lesion for a (D, H, W) volume."""
+    nbytes = L.load().rehr_seg_cc_workspace_bytes(*dims)
+    if nbytes < 0:
+        L.check(int(nbytes), "rehr_seg_cc_workspace_bytes")
+    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+
+
+def seg_cc_roots(mask, connectivity, workspace=None):
+    """mask: uint8 (D, H, W), non-zero = foreground.  Returns (roots int32 (D, H, W), workspace): the smallest linear
+    index of every voxel's component, -1 at background (rehr_seg_cc_roots_i32)."""
+    _chk_eval(mask, torch.uint8, "seg_cc_roots mask", 3)
+    dims = seg_cc_check_extent(mask.shape)
+    conn = _cc_connectivity(connectivity)
+    if workspace is None:
+        workspace = seg_cc_workspace(dims, mask.device)
+    roots = torch.empty(dims, device=mask.device, dtype=torch.int32)
+    L.check(L.load().rehr_seg_cc_roots_i32(_ptr(mask), *dims, conn, _ptr(roots), _ptr(workspace), workspace.numel(),
+                                           _stream()), "rehr_seg_cc_roots_i32")
+    return roots, workspace
+
+
+def seg_cc_compact(roots, count):
+    """roots: seg_cc_roots' map.  Returns labels int32 of its shape, 1..n in the order of the roots and 0 at
+    background; count (int64 [1], zeroed) += n.  The prefix sum between is torch's cumsum (rehr_seg_cc_compact_i32)."""
+    _chk_eval(roots, torch.int32, "seg_cc_compact roots", 3)
+    _chk_eval(count, torch.int64, "seg_cc_compact count", 1)
+    seg_cc_check_extent(roots.shape)
+    if count.numel() != 1:
+        raise L.RehrsegHipError("seg_cc_compact: 1 count")
+    n = roots.numel()
+    flat = roots.view(-1)
+    rank = torch.cumsum((flat == torch.arange(n, device=roots.device, dtype=torch.int32)).to(torch.int32), 0,
+                        dtype=torch.int32)
+    labels = torch.empty_like(roots)
+    L.check(L.load().rehr_seg_cc_compact_i32(_ptr(roots), n, _ptr(rank), _ptr(labels), _ptr(count), _stream()),
+            "rehr_seg_cc_compact_i32")
+    return labels
+
+
+def seg_cc_lesion(roots_pred, roots_gt, out, workspace=None):
+    """out (int64 [8], zeroed) += n_pred, n_gt, tp_pred, tp_gt, the sizes of the largest component of either map, the
+    foreground of gt inside pred's largest, the foreground of gt (rehr_seg_cc_lesion_i64).  Returns the two packed
+    keys (size << 32) | (0xffffffff - root) of the largest components as an int64 [2] view of the workspace."""
+    _chk_eval(roots_pred, torch.int32, "seg_cc_lesion roots_pred", 3)
+    _chk_eval(roots_gt, torch.int32, "seg_cc_lesion roots_gt", 3)
+    _chk_eval(out, torch.int64, "seg_cc_lesion out", 1)
+    dims = seg_cc_check_extent(roots_pred.shape)
+    if tuple(roots_gt.shape) != dims or out.numel() != 8:
+        raise L.RehrsegHipError("seg_cc_lesion: roots_gt has roots_pred's shape, 8 outputs")
+    if workspace is None:
+        workspace = seg_cc_workspace(dims, roots_pred.device)
+    L.check(L.load().rehr_seg_cc_lesion_i64(_ptr(roots_pred), _ptr(roots_gt), roots_pred.numel(), _ptr(out),
+                                            _ptr(workspace), workspace.numel(), _stream()), "rehr_seg_cc_lesion_i64")
+    return workspace[:16].view(torch.int64)
+
+
 # ----------------------------------------------------------------------------- stage-1 -> stage-2 handoff (sr_volume.hip)
 def minmax_new(device, pairs=1):
     """`pairs` empty {min, max} code pairs (int32 storage of the kernels' order-preserving uint32 codes)."""

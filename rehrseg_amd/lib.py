@@ -203,6 +203,10 @@ PROTOTYPES = {
     "rehr_seg_surface_workspace_bytes": (_i64, [_i32] * 3),
     "rehr_seg_surface_dist_f32": (C.c_int, [_vp, _vp] + [_i32] * 3 + [_f32] * 3 + [_vp, _vp, _vp, _i64, _vp]),
     "rehr_seg_surface_reduce_f64": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "rehr_seg_cc_workspace_bytes": (_i64, [_i32] * 3),
+    "rehr_seg_cc_roots_i32": (C.c_int, [_vp] + [_i32] * 4 + [_vp, _vp, _i64, _vp]),
+    "rehr_seg_cc_lesion_i64": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "rehr_seg_cc_compact_i32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "rehr_minmax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "rehr_sr_window_gather_f32": (C.c_int, [_vp, _vp] + [_i32] * 8 + [_vp]),
     "rehr_sr_volume_scatter_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_vp, _vp, _vp, _vp, _vp]),

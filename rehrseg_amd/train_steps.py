@@ -221,10 +221,13 @@ def _report(dice, terms):
     return sum(dice) / len(dice)
 
 
-def _subject_line(name, dice, surf=None):
-    if surf is None:
-        return f"Subject {name}: {dice}"
-    return f"Subject {name}: {dice} | HD95: {surf['hd95']} | ASSD: {surf['assd']}"
+def _subject_line(name, dice, surf=None, les=None):
+    line = f"Subject {name}: {dice}"
+    if surf is not None:
+        line += f" | HD95: {surf['hd95']} | ASSD: {surf['assd']}"
+    if les is not None:
+        line += f" | Lesions: {les['tp_gt']}/{les['n_gt']} found, {les['fp']} false"
+    return line
 
 
 def _report_surface(surf):
@@ -242,8 +245,25 @@ def _report_surface(surf):
     print(f"Empty-surface cases: {sum(1 for s in surf if s['n_pred'] == 0 or s['n_gt'] == 0)} of {len(surf)}")
 
 
+def _report_lesions(les, dice):
+    """Lesion-wise totals over all cases with the micro-averaged precision, recall and F1, and nnU-Net's
+    post-processing decision: whether keeping only the largest predicted component raises the mean Dice."""
+    from .utils.seg_utils import _lesion_result
+    tot = {k: sum(c[k] for c in les) for k in ("n_pred", "n_gt", "tp_pred", "tp_gt", "fp", "fn")}
+    micro = _lesion_result([tot["n_pred"], tot["n_gt"], tot["tp_pred"], tot["tp_gt"], 0, 0, 0, 0])
+    print(f"Lesions: {tot['tp_gt']}/{tot['n_gt']} found, {tot['fn']} missed; "
+          f"{tot['n_pred']} predicted, {tot['fp']} false")
+    print(f"Lesion precision: {micro['precision']}")
+    print(f"Lesion recall: {micro['recall']}")
+    print(f"Lesion F1: {micro['f1']}")
+    mean, largest = sum(dice) / len(dice), sum(c["dice_largest"] for c in les) / len(les)
+    print(f"Average dice: {mean} | largest component only: {largest}")
+    print(f"Keep largest component: {'yes' if largest > mean else 'no'} "
+          f"({'raises' if largest > mean else 'does not raise'} the mean Dice)")
+
+
 def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1, *, device=None, surface=False,
-                   spacing=None):
+                   spacing=None, components=False, connectivity=26):
     """train_all.py:154-193 over in-memory cases: `cases` yields (name, image, label), each a (1, D, H, W) array or
     tensor (or a file name).  Prints the reference's summary and returns the mean Dice.
 
@@ -253,39 +273,54 @@ def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1
 
     With `surface=True` every subject's line gains HD95 and ASSD (evaluate_case's `surface` / `spacing`) and the
     summary their mean, std, max and min over the cases with finite values and the number of cases with an empty
-    surface; the return value stays the mean Dice."""
+    surface; the return value stays the mean Dice.
+
+    With `components=True` every subject's line gains `| Lesions: <tp_gt>/<n_gt> found, <fp> false` (evaluate_case's
+    `components` / `connectivity`) and the summary the totals over all cases, the micro-averaged lesion precision,
+    recall and F1, the mean Dice next to the mean Dice of the largest predicted component alone, and a last line
+    saying whether keeping only that component raises the mean Dice; the return value stays the mean Dice."""
     from .utils.seg_utils import _evaluate_case
-    dice, terms, surf = [], [], []
+    dice, terms, surf, les = [], [], [], []
     for name, img, label in cases:
-        out = _evaluate_case(model_seg, img, label, seperation, patch_size_ori[::-1], eval_HR, device, surface, spacing)
-        print(_subject_line(name, out[3], out[5] if surface else None))
+        out = _evaluate_case(model_seg, img, label, seperation, patch_size_ori[::-1], eval_HR, device, surface, spacing,
+                             components, connectivity)
+        print(_subject_line(name, out[3], out[5] if surface else None, out[-1] if components else None))
         dice.append(out[3])
         terms.append(out[4])
-        surf.extend(out[5:])
+        if surface:
+            surf.append(out[5])
+        if components:
+            les.append(out[-1])
     mean = _report(dice, terms)
     if surface:
         _report_surface(surf)
+    if components:
+        _report_lesions(les, dice)
     return mean
 
 
 def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path, fold, save_path=None, eval_HR=False,
-             seperation=1, surface=False):
+             seperation=1, surface=False, components=False, connectivity=26):
     """train_all.py:154-193: every validation subject of the split's fold, read with SimpleITK; with `save_path`, the
     predictions are written next to it as NIfTI via SimpleITK as the reference does.  `surface`: as evaluate_cases',
-    in the units of each image file's spacing."""
+    in the units of each image file's spacing.  `components`, `connectivity`: as evaluate_cases'."""
     import json
     import os
     from .utils.seg_utils import _evaluate_case, _sitk
     sitk = _sitk()
     with open(split_path, "r") as f:
         split_data = json.load(f)[fold]["val"]
-    dice, terms, surf = [], [], []
+    dice, terms, surf, les = [], [], [], []
     for subject in split_data:
         test_img = os.path.join(val_img_path, subject + "_0000.nii.gz")
         test_label = os.path.join(val_label_path, subject + ".nii.gz")
         pred_lr, pred_hr, _, dice_lr, t, *s = _evaluate_case(model_seg, test_img, test_label, seperation,
-                                                              patch_size_ori[::-1], eval_HR, None, surface)
-        surf.extend(s)
+                                                              patch_size_ori[::-1], eval_HR, None, surface, None,
+                                                              components, connectivity)
+        if surface:
+            surf.append(s[0])
+        if components:
+            les.append(s[-1])
         if save_path is not None:
             os.makedirs(os.path.join(save_path, "val"), exist_ok=True)
             ori = sitk.ReadImage(test_img)
@@ -301,10 +336,12 @@ def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path
                 img.SetOrigin(ori.GetOrigin())
                 img.SetDirection(ori.GetDirection())
                 sitk.WriteImage(img, os.path.join(save_path, "val", f"{subject}_pred_hr.nii.gz"))
-        print(_subject_line(subject, dice_lr, s[0] if surface else None))
+        print(_subject_line(subject, dice_lr, s[0] if surface else None, s[-1] if components else None))
         dice.append(dice_lr)
         terms.append(t)
     mean = _report(dice, terms)
     if surface:
         _report_surface(surf)
+    if components:
+        _report_lesions(les, dice)
     return mean

@@ -712,10 +712,102 @@ def surface_distance_metrics(prediction, ground_truth, spacing=(1., 1., 1.), *, 
     return _surface_result(out.cpu().numpy())   # the one host sync
 
 
+# ----------------------------------------------------------------------------- components
+def _map_device(device, *maps):
+    if device is not None:
+        return torch.device(device)
+    on_dev = [a.device for a in maps if isinstance(a, torch.Tensor) and a.is_cuda]
+    return on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
+
+
+def _lesion_launch(be, pred, gt, connectivity, out):
+    """The component kernels on two uint8 maps on the device; out (int64 [8], zeroed) receives the eight integers of
+    rehr_seg_cc_lesion_i64.  No host sync; one workspace serves the three calls."""
+    roots_pred, workspace = be.seg_cc_roots(pred, connectivity)
+    roots_gt, _ = be.seg_cc_roots(gt, connectivity, workspace)
+    be.seg_cc_lesion(roots_pred, roots_gt, out, workspace)
+
+
+def _ratio(num, den):
+    return num / den if den else float("nan")
+
+
+def _lesion_result(vals):
+    """The host form of _lesion_launch's eight int64."""
+    n_pred, n_gt, tp_pred, tp_gt, largest_pred, largest_gt, inter, sum_gt = (int(v) for v in vals)
+    precision, recall = _ratio(tp_pred, n_pred), _ratio(tp_gt, n_gt)
+    if np.isnan(precision) or np.isnan(recall):
+        f1 = float("nan")
+    else:
+        f1 = 2 * precision * recall / (precision + recall) if precision + recall else 0.0
+    terms = (inter, largest_pred, sum_gt)
+    return {"n_pred": n_pred, "n_gt": n_gt, "tp_pred": tp_pred, "tp_gt": tp_gt, "fp": n_pred - tp_pred,
+            "fn": n_gt - tp_gt, "largest_pred": largest_pred, "largest_gt": largest_gt, "precision": precision,
+            "recall": recall, "f1": f1, "dice_largest": float(_dice_from_counts(*terms)), "dice_largest_terms": terms}
+
+
+def connected_components(mask, connectivity=26, *, device=None):
+    """(labels, n): the connected components of a mask, int32 labels (D, H, W) on the device and their number.
+
+    `mask`: a (D, H, W) or (1, D, H, W) numpy array or tensor of any dtype, host or device; non-zero is foreground.
+    `connectivity` 6, 18 or 26: scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3); outside the volume is
+    background.  Component k (1..n) is the one whose first voxel in raster order is the k-th such voxel; background is
+    0.  Everything runs on the device (csrc/seg_components.hip); reading n is the call's one host sync.  Raises
+    RehrsegHipError for more than 2**30 voxels or another connectivity."""
+    from .. import ops
+    from ..hip_backend import seg_cc_check_extent
+    be = ops.get_backend()
+    seg_cc_check_extent(_map_shape(mask))     # before any upload or launch
+    dev = _map_device(device, mask)
+    roots, _ = be.seg_cc_roots(_binary_u8(mask, dev), connectivity)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    labels = be.seg_cc_compact(roots, count)
+    return labels, int(count.cpu().numpy()[0])   # the one host sync
+
+
+def keep_largest_component(mask, connectivity=26, *, device=None):
+    """The mask reduced to its largest component: a uint8 device tensor of the mask's shape, 1 on that component and
+    0 elsewhere; among components of equal size the one whose first voxel comes first in raster order; all zero for an
+    empty mask.  Arguments as connected_components'.  No host sync."""
+    from .. import ops
+    from ..hip_backend import seg_cc_check_extent
+    be = ops.get_backend()
+    seg_cc_check_extent(_map_shape(mask))
+    dev = _map_device(device, mask)
+    roots, workspace = be.seg_cc_roots(_binary_u8(mask, dev), connectivity)
+    out = torch.zeros(8, dtype=torch.int64, device=dev)
+    key = be.seg_cc_lesion(roots, roots, out, workspace)[0]     # (size << 32) | (0xffffffff - root); 0 if empty
+    root = torch.where(key != 0, 0xffffffff - (key & 0xffffffff), -2)
+    return (roots == root).to(torch.uint8).reshape(tuple(mask.shape))
+
+
+def lesion_metrics(prediction, ground_truth, connectivity=26, *, device=None):
+    """Lesion-wise detection scores of two label maps: a dict of the ints `n_pred`, `n_gt` (the
+    numbers of components), `tp_pred` (predicted components holding a foreground voxel of the ground truth), `tp_gt`
+    (the reverse), `fp` = n_pred - tp_pred, `fn` = n_gt - tp_gt, `largest_pred`, `largest_gt` (voxels of the largest
+    component); the floats `precision` = tp_pred / n_pred, `recall` = tp_gt / n_gt (NaN for a zero denominator), `f1`
+    (NaN if either is NaN, 0.0 if both are 0); `dice_largest`, the Dice the case would have if only the largest
+    predicted component were kept, and its integer terms `dice_largest_terms` (intersection, prediction, label).
+
+    Arguments as connected_components'; both maps have one shape.  One host sync, the read of the eight integers."""
+    from .. import ops
+    from ..hip_backend import seg_cc_check_extent
+    be = ops.get_backend()
+    shape = _map_shape(prediction)
+    if _map_shape(ground_truth) != shape:
+        raise ValueError(f"prediction {shape} and ground truth {_map_shape(ground_truth)} differ in shape")
+    seg_cc_check_extent(shape)
+    dev = _map_device(device, prediction, ground_truth)
+    out = torch.zeros(8, dtype=torch.int64, device=dev)
+    _lesion_launch(be, _binary_u8(prediction, dev), _binary_u8(ground_truth, dev), connectivity, out)
+    return _lesion_result(out.cpu().numpy())   # the one host sync
+
+
 def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, device=None,
-                   surface=False, spacing=None):
+                   surface=False, spacing=None, components=False, connectivity=26):
     """evaluate_case, plus the exact Dice terms (intersection, sum of the prediction, sum of the label) and, with
-    `surface`, the boundary metrics of the LR maps as a sixth element."""
+    `surface`, the boundary metrics of the LR maps as a sixth element; with `components`, lesion_metrics' dict of the
+    LR maps as the last element."""
     from .. import ops
     be = ops.get_backend()
     model.eval()
@@ -732,7 +824,9 @@ def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, ge
     gt = _upload(torch.from_numpy(lr_label.squeeze(0).numpy().astype("uint8")), dev)
     slicers = _internal_get_sliding_window_slicers(padded, patch_size=patch)
     # with `surface`, the five numbers of the boundary metrics ride behind the eight stats in the same tensor
-    buf = torch.zeros(13 if surface else 8, dtype=torch.int64, device=dev)
+    # and with `components` the eight lesion integers behind those
+    n_surf = 5 if surface else 0
+    buf = torch.zeros(8 + n_surf + (8 if components else 0), dtype=torch.int64, device=dev)
     stats = buf[:8].view(2, 4)
     with torch.no_grad():
         logits, counts = _fused_tiles(vol, pad, slicers, model, 0, False, 1, _device_gaussian(tuple(patch), str(dev)))
@@ -741,7 +835,9 @@ def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, ge
         del logits, counts
         lr_host = _to_host(labels_lr)
         if surface:
-            _surface_launch(be, labels_lr, gt, sp, buf[8:])
+            _surface_launch(be, labels_lr, gt, sp, buf[8:13])
+        if components:
+            _lesion_launch(be, labels_lr, gt, connectivity, buf[8 + n_surf:])
         if get_HR_results:
             # the reference's HR branch: no Gaussian, no softmax, and the padding is not reverted
             logits, counts = _fused_tiles(vol, pad, slicers, model, 1, True, sep, None)
@@ -756,11 +852,15 @@ def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, ge
     prediction_hr = hr_host.numpy() if get_HR_results else prediction_lr
     terms = tuple(int(v) for v in st[0, 1:])
     out = (prediction_lr, prediction_hr, lr_label, _dice_from_counts(*terms), terms)
-    return out + (_surface_result(host[8:]),) if surface else out
+    if surface:
+        out += (_surface_result(host[8:13]),)
+    if components:
+        out += (_lesion_result(host[8 + n_surf:]),)
+    return out
 
 
 def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, *, device=None,
-                  surface=False, spacing=None):
+                  surface=False, spacing=None, components=False, connectivity=26):
     """ref :736-784 on the device: (prediction_lr uint8 (D, H, W), prediction_hr, lr_label float (1, D, H, W) CPU
     tensor, dice_lr float64).
 
@@ -778,7 +878,11 @@ def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get
     With `surface=True` a fifth element follows: surface_distance_metrics' dict for the LR prediction against the LR
     label, in the units of `spacing` = (sd, sh, sw), else of the image file's properties['spacing'], else (1, 1, 1).
     The surface kernels run on the two maps while they are on the device and their results travel with the same
-    read: still one host sync.  With `surface=False` nothing changes."""
+    read: still one host sync.  With `surface=False` nothing changes.
+
+    With `components=True` the last element is lesion_metrics' dict for the LR prediction against the LR label at
+    `connectivity` (after the surface dict if both are asked for); its eight integers travel with the same read as
+    well.  With `components=False` nothing changes."""
     out = _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results, device, surface,
-                         spacing)
+                         spacing, components, connectivity)
     return out[:4] + out[5:]
