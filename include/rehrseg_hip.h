@@ -759,6 +759,44 @@ int rehr_seg_cc_compact_i32(const int32_t* roots, int64_t N, const int32_t* rank
                             void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Intensity normalisation on the device (utils/seg_utils.py:74-135 percentile_normalization, zeroone_normalization;
+ * rehrseg_amd/utils/seg_utils.py drives them, csrc/intensity_norm.hip).  Items are dense runs of S fp32
+ * values, item b starting `stride` elements after item b - 1 (4-byte aligned; 16-byte loads where an item start is
+ * 16-byte aligned, a scalar head and tail otherwise).  S <= 2^30, B <= 65535, R <= REHR_ORDER_STATS_MAX_RANKS,
+ * Q <= REHR_PERCENTILE_MAX_Q: REHR_ENOSUP above; a null pointer, a size < 1, a rank outside [0, S), a misaligned
+ * pointer or too small a workspace: REHR_EINVAL; all before any launch.  Every call is a fixed number of launches and
+ * reads nothing back.
+ * ------------------------------------------------------------------------- */
+#define REHR_ORDER_STATS_MAX_RANKS 8
+#define REHR_PERCENTILE_MAX_Q 4
+/* Bytes of the workspace of rehr_order_stats_f32 (16 per (item, rank), 4 per item, 1024 per (item, rank), each part
+ * rounded up to 16), or the error code. */
+int64_t rehr_order_stats_workspace_bytes(int32_t B, int32_t R);
+/* out[b][r] = sort(x[b][0..S))[ranks[r]]: the exact float, bit for bit the value an ascending sort puts at that index
+ * (-0 and +0 are distinct keys here, -0 first; a sort that treats them as equal may leave either).  An item that holds
+ * a NaN gets the quiet NaN 0x7fc00000 in every rank; +-inf are ordinary values.  `ranks`: R host integers, read during
+ * the call, the same for every item.  MSD radix select on the order-preserving 32-bit key, four digits of 8 bits,
+ * integer counts only: the same bits on every run.  workspace: 16-byte aligned, overwritten. */
+int rehr_order_stats_f32(const float* x, int32_t B, int64_t S, int64_t item_stride, const int64_t* ranks, int32_t R,
+                         float* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* out[b][j] (fp64) = numpy.percentile's 'linear' value from stats[b][2 j] = sorted[floor h_j] and stats[b][2 j + 1] =
+ * sorted[min(floor h_j + 1, S - 1)] (fp32 [B][2 Q], rehr_order_stats_f32's output) and t[j] = h_j - floor h_j (Q host
+ * doubles in [0, 1), h_j = q_j / 100 * (S - 1) formed by the caller): with a, b widened to fp64 and d = b - a,
+ * t >= 0.5 ? b - d * (1 - t) : a + d * t, every operation rounded on its own.  With strictly_positive != 0 a negative
+ * out[b][0] becomes 0 (_percentile_norm's v_min). */
+int rehr_percentile_f64(const float* stats, int32_t B, int32_t Q, const double* t, int32_t strictly_positive,
+                        double* out, void* stream);
+#define REHR_INTENSITY_PERCENTILE 0 /* y = (min(max(x, lo), hi) - lo) / (hi - lo); a NaN stays a NaN */
+#define REHR_INTENSITY_ZEROONE 1    /* y = (x - lo) / (hi - lo) */
+/* One streaming pass over x[b][0..S) into y[b][0..S) (strides in elements; y may be x) with lo = (float)bounds[b *
+ * bounds_stride], hi = (float)bounds[b * bounds_stride + 1] read on the device (fp64: rehr_percentile_f64's output
+ * with stride 2, or the {min, max} of rehr_aug_stats_f32 with stride 4).  IEEE fp32 subtractions and a correctly
+ * rounded fp32 division, no reciprocal and no FMA: the bits of the same numpy float32 expression.  hi == lo gives
+ * 0 / 0 = NaN, NaN bounds give NaN everywhere. */
+int rehr_intensity_apply_f32(const float* x, float* y, int32_t B, int64_t S, int64_t x_stride, int64_t y_stride,
+                             int32_t mode, const double* bounds, int64_t bounds_stride, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Stage-1 -> stage-2 volume handoff on the device (utils/sr_utils.py:137-242 inference_flavr, :279-304 zeroonenorm /
  * postprocess_flavr; rehrseg_amd/utils/sr_utils.py drives them, csrc/sr_volume.hip).
  * A "minmax" buffer is two uint32 codes {min, max} that order like the floats they stand for:

@@ -1490,6 +1490,112 @@ def seg_cc_lesion(roots_pred, roots_gt, out, workspace=None):
     return workspace[:16].view(torch.int64)
 
 
+# ----------------------------------------------------------------------------- intensity normalisation (intensity_norm.hip)
+ORDER_STATS_MAX_RANKS, PERCENTILE_MAX_Q = 8, 4
+INTENSITY_MAX_VOXELS, INTENSITY_MAX_ITEMS = 1 << 30, 65535
+INTENSITY_PERCENTILE, INTENSITY_ZEROONE = 0, 1
+
+
+def _item_runs(x, what):
+    """(B, S, stride) of a float32 device tensor whose items x[b] are dense runs of S elements, stride elements apart
+    (a contiguous (B, ...) tensor, or channel 0 of a contiguous (B, C, ...) one)."""
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() < 1:
+        raise L.RehrsegHipError(f"{what}: float32 device tensor (B, ...) (no CPU fallback)")
+    B = x.shape[0]
+    S = x.numel() // max(B, 1)
+    if B < 1 or S < 1 or not x[0].is_contiguous():
+        raise L.RehrsegHipError(f"{what}: at least one item, every item a dense run")
+    if B > INTENSITY_MAX_ITEMS or S > INTENSITY_MAX_VOXELS:
+        raise L.RehrsegHipError(f"{what}: at most 65535 items of at most 2**30 elements (REHR_ENOSUP)")
+    return B, S, (x.stride(0) if B > 1 else S)
+
+
+def order_stats_workspace(B, R, device):
+    """The workspace of order_stats for B items and R ranks."""
+    nbytes = L.load().rehr_order_stats_workspace_bytes(B, R)
+    if nbytes < 0:
+        L.check(int(nbytes), "rehr_order_stats_workspace_bytes")
+    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+
+
+def order_stats(x, ranks, out=None, workspace=None):
+    """x (B, ...) float32 on the device, every item a dense run (see _item_runs); ranks: up to 8 Python ints in
+    [0, S).  Returns float32 (B, R): out[b][r] = sort(x[b])[ranks[r]], NaN for an item with a NaN
+    (rehr_order_stats_f32).  No host sync."""
+    B, S, stride = _item_runs(x, "order_stats")
+    ranks = [int(k) for k in ranks]
+    R = len(ranks)
+    if not 1 <= R <= ORDER_STATS_MAX_RANKS or min(ranks) < 0 or max(ranks) >= S:
+        raise L.RehrsegHipError(f"order_stats: 1..8 ranks inside [0, {S}), got {ranks}")
+    if out is None:
+        out = torch.empty((B, R), device=x.device, dtype=torch.float32)
+    _chk_eval(out, torch.float32, "order_stats out", 2)
+    if tuple(out.shape) != (B, R):
+        raise L.RehrsegHipError("order_stats: out is (B, R)")
+    if workspace is None:
+        workspace = order_stats_workspace(B, R, x.device)
+    L.check(L.load().rehr_order_stats_f32(_ptr(x), B, S, stride, (C.c_int64 * R)(*ranks), R, _ptr(out),
+                                          _ptr(workspace), workspace.numel(), _stream()), "rehr_order_stats_f32")
+    return out
+
+
+def percentile_plan(S, q):
+    """numpy.percentile's virtual indices for S elements, in Python floats: (ranks [k0, k1 per q], t per q) with
+    h = q / 100 * (S - 1), k0 = floor(h), k1 = min(k0 + 1, S - 1), t = h - k0."""
+    ranks, ts = [], []
+    for p in q:
+        p = float(p)
+        if not 0.0 <= p <= 100.0:
+            raise ValueError(f"percentiles must be in the range [0, 100], got {p!r}")
+        h = (p / 100.0) * (S - 1)
+        k0 = min(int(h // 1), S - 1)
+        ranks += [k0, min(k0 + 1, S - 1)]
+        ts.append(h - k0)
+    return ranks, ts
+
+
+def percentile_bounds(stats, t, strictly_positive=False, out=None):
+    """stats: order_stats' (B, 2 Q) for percentile_plan's ranks, t: its Q fractions.  Returns float64 (B, Q): numpy's
+    'linear' percentiles; with strictly_positive a negative first column becomes 0 (rehr_percentile_f64)."""
+    _chk_eval(stats, torch.float32, "percentile_bounds stats", 2)
+    t = [float(v) for v in t]
+    B, Q = stats.shape[0], len(t)
+    if not 1 <= Q <= PERCENTILE_MAX_Q or stats.shape[1] != 2 * Q:
+        raise L.RehrsegHipError("percentile_bounds: 1..4 percentiles, two order statistics each")
+    if out is None:
+        out = torch.empty((B, Q), device=stats.device, dtype=torch.float64)
+    _chk_eval(out, torch.float64, "percentile_bounds out", 2)
+    if tuple(out.shape) != (B, Q):
+        raise L.RehrsegHipError("percentile_bounds: out is (B, Q)")
+    L.check(L.load().rehr_percentile_f64(_ptr(stats), B, Q, (C.c_double * Q)(*t), int(bool(strictly_positive)),
+                                         _ptr(out), _stream()), "rehr_percentile_f64")
+    return out
+
+
+def intensity_apply(x, bounds, mode, out=None):
+    """y[b] = (clip(x[b], lo, hi) - lo) / (hi - lo) (INTENSITY_PERCENTILE) or (x[b] - lo) / (hi - lo)
+    (INTENSITY_ZEROONE) with {lo, hi} = the first two entries of bounds[b] (float64 (B, >= 2) on the device, rows
+    dense) rounded to fp32.  x as order_stats'; out: a contiguous tensor of B * S elements, or x itself for in place
+    (rehr_intensity_apply_f32).  Returns out."""
+    B, S, stride = _item_runs(x, "intensity_apply")
+    if not bounds.is_cuda or bounds.dtype != torch.float64 or bounds.dim() != 2 or bounds.shape[0] != B or \
+            bounds.shape[1] < 2 or bounds.stride(1) != 1 or (B > 1 and bounds.stride(0) < 2):
+        raise L.RehrsegHipError("intensity_apply: bounds float64 (B, >= 2) on the device")
+    if out is None:
+        out = torch.empty((B, S), device=x.device, dtype=torch.float32)
+    if out is x:
+        ystride = stride
+    else:
+        _chk_eval(out, torch.float32, "intensity_apply out")
+        if out.numel() != B * S:
+            raise L.RehrsegHipError("intensity_apply: out holds B * S elements")
+        ystride = S
+    L.check(L.load().rehr_intensity_apply_f32(_ptr(x), _ptr(out), B, S, stride, ystride, int(mode), _ptr(bounds),
+                                              bounds.stride(0) if B > 1 else 2, _stream()),
+            "rehr_intensity_apply_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- stage-1 -> stage-2 handoff (sr_volume.hip)
 def minmax_new(device, pairs=1):
     """`pairs` empty {min, max} code pairs (int32 storage of the kernels' order-preserving uint32 codes)."""

@@ -263,7 +263,7 @@ def _report_lesions(les, dice):
 
 
 def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1, *, device=None, surface=False,
-                   spacing=None, components=False, connectivity=26):
+                   spacing=None, components=False, connectivity=26, norm="zscore"):
     """train_all.py:154-193 over in-memory cases: `cases` yields (name, image, label), each a (1, D, H, W) array or
     tensor (or a file name).  Prints the reference's summary and returns the mean Dice.
 
@@ -278,12 +278,15 @@ def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1
     With `components=True` every subject's line gains `| Lesions: <tp_gt>/<n_gt> found, <fp> false` (evaluate_case's
     `components` / `connectivity`) and the summary the totals over all cases, the micro-averaged lesion precision,
     recall and F1, the mean Dice next to the mean Dice of the largest predicted component alone, and a last line
-    saying whether keeping only that component raises the mean Dice; the return value stays the mean Dice."""
+    saying whether keeping only that component raises the mean Dice; the return value stays the mean Dice.
+
+    `norm`: evaluate_case's ("zscore" on the host by default, None, or "percentile" / ("percentile", p_min, p_max) /
+    "zeroone" on the device)."""
     from .utils.seg_utils import _evaluate_case
     dice, terms, surf, les = [], [], [], []
     for name, img, label in cases:
         out = _evaluate_case(model_seg, img, label, seperation, patch_size_ori[::-1], eval_HR, device, surface, spacing,
-                             components, connectivity)
+                             components, connectivity, norm)
         print(_subject_line(name, out[3], out[5] if surface else None, out[-1] if components else None))
         dice.append(out[3])
         terms.append(out[4])
@@ -300,10 +303,10 @@ def evaluate_cases(model_seg, cases, patch_size_ori, eval_HR=False, seperation=1
 
 
 def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path, fold, save_path=None, eval_HR=False,
-             seperation=1, surface=False, components=False, connectivity=26):
+             seperation=1, surface=False, components=False, connectivity=26, norm="zscore"):
     """train_all.py:154-193: every validation subject of the split's fold, read with SimpleITK; with `save_path`, the
     predictions are written next to it as NIfTI via SimpleITK as the reference does.  `surface`: as evaluate_cases',
-    in the units of each image file's spacing.  `components`, `connectivity`: as evaluate_cases'."""
+    in the units of each image file's spacing.  `components`, `connectivity`, `norm`: as evaluate_cases'."""
     import json
     import os
     from .utils.seg_utils import _evaluate_case, _sitk
@@ -316,7 +319,7 @@ def evaluate(model_seg, patch_size_ori, val_img_path, val_label_path, split_path
         test_label = os.path.join(val_label_path, subject + ".nii.gz")
         pred_lr, pred_hr, _, dice_lr, t, *s = _evaluate_case(model_seg, test_img, test_label, seperation,
                                                               patch_size_ori[::-1], eval_HR, None, surface, None,
-                                                              components, connectivity)
+                                                              components, connectivity, norm)
         if surface:
             surf.append(s[0])
         if components:

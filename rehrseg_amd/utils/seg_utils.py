@@ -1,6 +1,7 @@
 """Losses and normalisation used by the two training loops, under the reference's import
-path (`utils.seg_utils`): same names, arguments and numerics as utils/seg_utils.py:137-156
-(zscore_normalization), :289-372 (RobustCrossEntropyLoss, DC_and_weighted_CE_loss,
+path (`utils.seg_utils`): same names, arguments and numerics as utils/seg_utils.py:74-156
+(percentile_normalization, zeroone_normalization -- on the device for device tensors, csrc/intensity_norm.hip, DESIGN
+section 3.17 -- and zscore_normalization), :289-372 (RobustCrossEntropyLoss, DC_and_weighted_CE_loss,
 _build_loss, with nnunetv2's DeepSupervisionWrapper restated) and :786-885 (DiceLoss, BCEDiceLoss).
 
 The stage-2 loss (`DC_and_weighted_CE_loss`) runs as one fused HIP pass over the logits each way when
@@ -39,6 +40,168 @@ def zscore_normalization(image):
         view /= max(std, 1e-8)
         outs.append(view)
     return torch.stack(outs, dim=0)
+
+
+# ----------------------------------------------------------------------------- percentile / zero-one
+def _percentile_norm(input_tensor, reference_tensor=None, p_min=0.5, p_max=99.5, strictlyPositive=True):
+    """ref :74-98 on the host: clip to the two percentiles (the lower one raised to 0 with strictlyPositive), scale to
+    [0, 1].  Only reference_tensor=None is reachable from the public function."""
+    if reference_tensor is None:
+        reference_tensor = input_tensor
+    v_min, v_max = np.percentile(reference_tensor, [p_min, p_max])
+    if v_min < 0 and strictlyPositive:
+        v_min = 0
+    output_tensor = np.clip(input_tensor, v_min, v_max)
+    return (output_tensor - v_min) / (v_max - v_min)
+
+
+def _channel0_runs(image, what):
+    """image[:, 0] of a (B, C, ...) device tensor, every item one dense run; ValueError for any other layout."""
+    if image.dim() < 2:
+        raise ValueError(f"{what}: expected a (B, C, ...) tensor, got {tuple(image.shape)}")
+    ch = image[:, 0]
+    if ch.numel() == 0 or not ch[0].is_contiguous():
+        raise ValueError(f"{what}: channel 0 of every item must be one dense run (C == 1 or a contiguous NCDHW "
+                         f"tensor); got shape {tuple(image.shape)} with strides {tuple(image.stride())} "
+                         "(channels-last?): call .contiguous() first")
+    return ch
+
+
+def _percentile_normalization_device(image, p_min=0.5, p_max=99.5, strictlyPositive=True):
+    """percentile_normalization of a device tensor: two order statistics per percentile by radix select, numpy's
+    lerp and the clip / scale pass, all on the device and without a host sync (csrc/intensity_norm.hip)."""
+    from .. import ops
+    from ..hip_backend import INTENSITY_PERCENTILE, percentile_plan
+    be = ops.get_backend()
+    ch = _channel0_runs(image, "percentile_normalization")
+    if ch.dtype != torch.float32:
+        ch = ch.to(torch.float32)
+    S = ch[0].numel()
+    ranks, t = percentile_plan(S, (p_min, p_max))
+    bounds = be.percentile_bounds(be.order_stats(ch, ranks), t, strictlyPositive)
+    out = be.intensity_apply(ch, bounds, INTENSITY_PERCENTILE)
+    return out.view((image.shape[0], 1) + tuple(image.shape[2:]))
+
+
+def _zeroone_normalization_device(image):
+    """zeroone_normalization of a float32 device tensor, channel 0 rewritten in place; returns that channel as a
+    (B, 1, ...) view of `image`.  No host sync."""
+    from .. import ops
+    from ..hip_backend import INTENSITY_ZEROONE
+    be = ops.get_backend()
+    ch = _channel0_runs(image, "zeroone_normalization")
+    if ch.dtype != torch.float32:
+        raise ValueError(f"zeroone_normalization writes the caller's tensor in place: float32 on the device, got "
+                         f"{ch.dtype}")
+    if ch.is_contiguous():
+        stats = be.aug_stats(ch)
+    else:       # C > 1: the items are apart, one statistics call each
+        stats = torch.empty((ch.shape[0], 4), dtype=torch.float64, device=ch.device)
+        for b in range(ch.shape[0]):
+            be.aug_stats(ch[b:b + 1], out=stats[b:b + 1])
+    be.intensity_apply(ch, stats[:, 2:], INTENSITY_ZEROONE, out=ch)
+    return image[:, 0:1]
+
+
+def percentile_normalization(image, p_min=0.5, p_max=99.5, strictlyPositive=True):
+    """ref :100-114: clip channel 0 of every item at its p_min / p_max percentiles and scale to [0, 1]; returns
+    (B, 1, ...), or the normalised array for a numpy array (taken as one item).
+
+    numpy arrays and CPU tensors run on the host as the reference's lines do.  A device tensor stays on the device
+    (DESIGN section 3.17): the result is a float32 device tensor (B, 1, ...), the input is not written and the call
+    makes no host sync.  Deviation: the reference moves a device tensor to the CPU and, under numpy 2, returns
+    float64; here the bounds are numpy's float64 percentiles rounded to float32 and the clip, the subtraction and the
+    division are float32.  Channel 0 of every item must be one dense run (C == 1 or contiguous NCDHW), ValueError
+    otherwise.  An item with a NaN, or with v_max == v_min, comes back all NaN, as from the reference."""
+    if isinstance(image, torch.Tensor):
+        if image.is_cuda:
+            return _percentile_normalization_device(image, p_min, p_max, strictlyPositive)
+        out_imgs = []
+        for i in range(image.shape[0]):
+            img = image[i:i + 1, 0, ...].cpu().numpy()
+            img = _percentile_norm(img, p_min=p_min, p_max=p_max, strictlyPositive=strictlyPositive)
+            out_imgs.append(torch.from_numpy(img))
+        return torch.stack(out_imgs, dim=0)
+    image = image.astype(np.float32, copy=False)
+    return _percentile_norm(image, p_min=p_min, p_max=p_max, strictlyPositive=strictlyPositive)
+
+
+def zeroone_normalization(image):
+    """ref :116-135: (x - min) / (max - min) of channel 0 of every item, IN PLACE on the caller's tensor (or float32
+    array); returns the normalised channel as (B, 1, ...).  A device tensor (float32, channel 0 of every item one
+    dense run) is rewritten by the kernels without a host sync; min and max come from rehr_aug_stats_f32, which skips
+    NaNs where torch's min / max would return NaN.  A constant item gives 0 / 0 = NaN, as the reference."""
+    if isinstance(image, torch.Tensor):
+        if image.is_cuda:
+            return _zeroone_normalization_device(image).clone()     # the reference's torch.stack copies as well
+        out_imgs = []
+        for i in range(image.shape[0]):
+            img = image[i:i + 1, 0, ...]
+            lo, hi = img.min(), img.max()
+            img -= lo
+            img /= (hi - lo)
+            out_imgs.append(img)
+        return torch.stack(out_imgs, dim=0)
+    image = image.astype(np.float32, copy=False)
+    lo, hi = image.min(), image.max()
+    image -= lo
+    image /= (hi - lo)
+    return image
+
+
+def intensity_percentiles(image, q, *, device=None):
+    """numpy.percentile(image[b].astype(float64), q) for every item b of `image` (B, ...), as a (B, len(q)) float64
+    tensor on the device, without a host sync: exact order statistics by radix select and numpy's 'linear' lerp in
+    fp64.  `image`: a numpy array or a tensor, host or device, converted to float32; `q`: up to 4
+    percentiles in [0, 100].  An item with a NaN gives NaN.  `device` defaults to a device tensor's, else the current
+    device."""
+    from .. import ops
+    from ..hip_backend import PERCENTILE_MAX_Q, percentile_plan
+    be = ops.get_backend()
+    q = [float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))]
+    if not 1 <= len(q) <= PERCENTILE_MAX_Q:
+        raise ValueError(f"intensity_percentiles: 1 to {PERCENTILE_MAX_Q} percentiles per call, got {len(q)}")
+    dev = _map_device(device, image)
+    if isinstance(image, torch.Tensor):
+        t = image.detach().to(torch.float32)
+        if t.device != dev:
+            t = t.to(dev) if t.is_cuda else _upload(t.contiguous(), dev)
+    else:
+        t = _upload(torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)), dev)
+    if t.dim() < 1 or t.numel() == 0:
+        raise ValueError(f"intensity_percentiles: expected a non-empty (B, ...) volume, got {tuple(t.shape)}")
+    t = t.contiguous()
+    ranks, frac = percentile_plan(t[0].numel(), q)
+    return be.percentile_bounds(be.order_stats(t, ranks), frac, False)
+
+
+def _norm_spec(norm, also=()):
+    """The device normalisations by name: 'percentile' -> ('percentile', 0.5, 99.5), ('percentile', lo, hi),
+    'zeroone' -> ('zeroone',); a value in `also` is returned as it is; anything else raises ValueError."""
+    if any(norm is a or (isinstance(a, str) and isinstance(norm, str) and norm == a) for a in also):
+        return norm
+    if isinstance(norm, str) and norm == "percentile":
+        return ("percentile", 0.5, 99.5)
+    if isinstance(norm, str) and norm == "zeroone":
+        return ("zeroone",)
+    if isinstance(norm, (tuple, list)) and len(norm) == 3 and norm[0] == "percentile":
+        lo, hi = float(norm[1]), float(norm[2])
+        if not 0.0 <= lo < hi <= 100.0:
+            raise ValueError(f"norm: percentiles 0 <= p_min < p_max <= 100, got {norm!r}")
+        return ("percentile", lo, hi)
+    names = [repr(a) for a in also] + ["'percentile'", "('percentile', p_min, p_max)", "'zeroone'"]
+    raise ValueError(f"norm: one of {', '.join(names)}; got {norm!r}")
+
+
+def _normalize_on_device(vol, spec):
+    """One float32 volume of any shape on the device, normalised as _norm_spec's `spec` says: a new tensor of the
+    same shape, no host sync."""
+    x = vol.to(torch.float32).contiguous().view((1, 1) + tuple(vol.shape))
+    if spec[0] == "percentile":
+        return _percentile_normalization_device(x, spec[1], spec[2], True).view(tuple(vol.shape))
+    if x.data_ptr() == vol.data_ptr():      # the caller's volume is not written
+        x = x.clone()
+    return _zeroone_normalization_device(x).view(tuple(vol.shape))
 
 
 class RobustCrossEntropyLoss(nn.CrossEntropyLoss):
@@ -804,16 +967,17 @@ def lesion_metrics(prediction, ground_truth, connectivity=26, *, device=None):
 
 
 def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, device=None,
-                   surface=False, spacing=None, components=False, connectivity=26):
+                   surface=False, spacing=None, components=False, connectivity=26, norm="zscore"):
     """evaluate_case, plus the exact Dice terms (intersection, sum of the prediction, sum of the label) and, with
     `surface`, the boundary metrics of the LR maps as a sixth element; with `components`, lesion_metrics' dict of the
     LR maps as the last element."""
     from .. import ops
     be = ops.get_backend()
+    spec = _norm_spec(norm, also=("zscore", None))
     model.eval()
     sep = _integral_separation(slice_separation)
     dev = torch.device(device) if device is not None else _model_device(model)
-    lr_data, properties = preprocess_image(case_img)
+    lr_data, properties = preprocess_image(case_img, apply_norm=spec == "zscore")
     lr_label, _ = preprocess_image(case_label, apply_norm=False)
     if surface:
         sp = _spacing_f32(spacing if spacing is not None else properties.get("spacing", (1., 1., 1.)))
@@ -821,6 +985,8 @@ def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, ge
     padded, pad, _ = _pad_geometry(lr_data.shape[1:], patch)
     revert = tuple(slice(b, b + n) for b, n in zip(pad, lr_data.shape[1:]))
     vol = _upload(lr_data[0], dev)
+    if isinstance(spec, tuple):     # the raw volume, normalised on the device in front of the tiles: no host sync
+        vol = _normalize_on_device(vol, spec)
     gt = _upload(torch.from_numpy(lr_label.squeeze(0).numpy().astype("uint8")), dev)
     slicers = _internal_get_sliding_window_slicers(padded, patch_size=patch)
     # with `surface`, the five numbers of the boundary metrics ride behind the eight stats in the same tensor
@@ -860,7 +1026,7 @@ def _evaluate_case(model, case_img, case_label, slice_separation, patch_size, ge
 
 
 def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results=False, *, device=None,
-                  surface=False, spacing=None, components=False, connectivity=26):
+                  surface=False, spacing=None, components=False, connectivity=26, norm="zscore"):
     """ref :736-784 on the device: (prediction_lr uint8 (D, H, W), prediction_hr, lr_label float (1, D, H, W) CPU
     tensor, dice_lr float64).
 
@@ -882,7 +1048,12 @@ def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get
 
     With `components=True` the last element is lesion_metrics' dict for the LR prediction against the LR label at
     `connectivity` (after the surface dict if both are asked for); its eight integers travel with the same read as
-    well.  With `components=False` nothing changes."""
+    well.  With `components=False` nothing changes.
+
+    `norm`: "zscore" (default) is the host z-score above; None feeds the volume as it is; "percentile",
+    ("percentile", p_min, p_max) and "zeroone" upload the raw volume and normalise it on the device in front of the
+    tiles (percentile_normalization / zeroone_normalization's kernels): still one host sync.
+    Anything else raises ValueError."""
     out = _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results, device, surface,
-                         spacing, components, connectivity)
+                         spacing, components, connectivity, norm)
     return out[:4] + out[5:]

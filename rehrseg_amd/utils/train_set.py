@@ -27,7 +27,8 @@ import torch
 from .. import hip_backend as hb
 from .pad import get_pads
 from .augment import DEEP_SUPERVISION_SCALES
-from .seg_utils import get_training_transforms, zscore_normalization
+from .seg_utils import (_norm_spec, _normalize_on_device, get_training_transforms, zeroone_normalization,  # noqa: F401
+                        zscore_normalization)
 
 _ROTATION_FOR_DA = {"x": (-np.pi, np.pi), "y": (0, 0), "z": (0, 0)}  # utils/train_set.py:61, :260
 
@@ -337,7 +338,11 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
     `deep_supervision` (port only: the reference hard-codes a local, :65-69): the reference's scale table goes to the
     transform chain ("nnunet"), or, with another or no train_transform, to the pyramid step alone behind it; label_lr
     (and uncertainty_lr) then come back as lists with one (1, d, h, w) tensor per level ((B, 1, d, h, w) from `batch`).
-    The step draws no random numbers."""
+    The step draws no random numbers.
+    `norm`: True (the reference's z-score) or False as before; "percentile", ("percentile", p_min, p_max) or "zeroone"
+    (port only) upload a host volume raw, take a device tensor as it is, and normalise the volume once on the device
+    with percentile_normalization / zeroone_normalization's kernels (no host sync); any other
+    value raises ValueError."""
 
     def __init__(self, image_path, split_subjects, slice_thickness, target_thickness, patch_size_ori, target_patch_size,
                  random_flip=False, uncertainty=False, preload=True, norm=True, device=None, volumes=None,
@@ -346,6 +351,10 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
         self.slice_thickness, self.target_thickness = slice_thickness, target_thickness
         self.separation = int(slice_thickness / target_thickness)
         self.random_flip, self.uncertainty, self.norm = random_flip, uncertainty, norm
+        spec = None
+        if not isinstance(norm, (bool, np.bool_, int, type(None))):
+            spec = _norm_spec(norm, also=(True, False))
+            norm = False
         self.target_patch_size = target_patch_size
         if isinstance(train_transform, str):
             if train_transform != "nnunet":
@@ -374,6 +383,8 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
                 if norm:
                     img = img - img.mean()
                     img = img / img.std(unbiased=False).clamp_min(1e-8)
+                if spec is not None:
+                    img = _normalize_on_device(img, spec)
                 self.imgs.append(img.contiguous())
                 self.labels.append(v["seg"].to(self.device, torch.uint8).contiguous())
                 self.uncertainties.append(v["uncertainty"].to(self.device, torch.uint8).contiguous()
@@ -382,7 +393,8 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
             img = np.asarray(v["img"])
             if norm:  # the reference normalises the whole volume on every access (:104-105): once is the same numbers
                 img = zscore_normalization(img.copy())
-            self.imgs.append(_dev(img, self.device, torch.float32))
+            img = _dev(img, self.device, torch.float32)
+            self.imgs.append(img if spec is None else _normalize_on_device(img, spec))
             self.labels.append(_dev(v["seg"], self.device, torch.uint8))
             self.uncertainties.append(_dev(v["uncertainty"], self.device, torch.uint8) if uncertainty else None)
         print("Total subjects", len(self.imgs))
