@@ -883,6 +883,35 @@ int rehr_sr_metrics_bf16(const void* pred, const int64_t* pred_strides, const fl
                          void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Stage-1 structure losses (rehrseg_amd/models/losses.py StructureLoss, csrc/sr_losses.hip): a differentiable
+ *   loss = l1 mean|p - t| + l2 mean (p - t)^2 + ssim (1 - mean S) + sobel mean|G(p) - G(t)|
+ * of input p against target t, logical (N, C, D, H, W) fp32 images each addressed by a base pointer and five element
+ * strides (>= 0; any layout, nothing is copied); every (H, W) slice is an image, V = N C D H W.
+ *   S  the SSIM index of rehr_sr_metrics_f32 (same window, constants, arithmetic and order of operations) over the
+ *      M = N C D (H - 10)(W - 10) valid window positions: 1 - the term is the mean index that entry point reports;
+ *   G  the Sobel magnitude sqrt(gx^2 + gy^2 + 1e-6) per slice, gx = [[-1,0,1],[-2,0,2],[-1,0,1]] / 8, gy its
+ *      transpose, replicate padding.
+ * A weight of 0 skips its term.  ssim != 0 needs H, W >= 11 (REHR_ENOSUP below); weights finite, data_range > 0.
+ * fwd: stats[n][4] double (written) = sum |p - t|, sum (p - t)^2, sum of S over the valid positions, sum |G(p) - G(t)|
+ *   of sample n (0 for a skipped term); *loss = the fp32 value; fields: NULL, or 3 V floats that receive the SSIM
+ *   coefficient fields the backward pass reads (only with ssim != 0).  Per-pixel terms fp32, every sum fp64 in a
+ *   fixed order: the same bits on every run; p == t gives exactly 0.  workspace:
+ *   rehr_structure_loss_workspace_bytes(N, C, D, H, W) bytes of device scratch, 8-byte aligned (< 0: REHR_E*).
+ * bwd: dinput (its own five strides, none 0 along an axis longer than 1) = *grad_output * d loss / d input, every
+ *   element written by one thread; |.| has derivative 0 at 0.  fields: what fwd wrote for the same operands and
+ *   weights (required with ssim != 0).  grad_output: one device float.
+ * ------------------------------------------------------------------------- */
+int64_t rehr_structure_loss_workspace_bytes(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W);
+int rehr_structure_loss_fwd_f32(const float* input, const int64_t* input_strides, const float* target,
+                                const int64_t* target_strides, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                float l1, float l2, float ssim, float sobel, float data_range, double* stats,
+                                float* loss, float* fields, void* workspace, int64_t workspace_bytes, void* stream);
+int rehr_structure_loss_bwd_f32(const float* input, const int64_t* input_strides, const float* target,
+                                const int64_t* target_strides, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                float l1, float l2, float ssim, float sobel, const float* fields,
+                                const float* grad_output, float* dinput, const int64_t* dinput_strides, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mixed-precision (*_bf16) variants of the HBM-bound fused-block kernels: the SAME arguments as the *_f32 entry
  * points above with every ACTIVATION pointer (x, y, res, dy, dx, dres) addressing bf16 elements (ld* in elements,
  * % 8 == 0, C % 8 == 0); gates, gamma / beta, mean_rstd stay fp32, statistics and reduction buffers fp64, the

@@ -1786,6 +1786,76 @@ def sr_metrics(pred, target, seg_logits=None, seg_target=None, data_range=1.0):
     return stats
 
 
+# ----------------------------------------------------------------------------- stage-1 structure losses (sr_losses.hip)
+def _structure_loss_operands(what, input, target, weights):
+    """-> (the two operands as 5-D views, the logical shape, the four weights as floats)."""
+    for t, name in ((input, "input"), (target, "target")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.RehrsegHipError(f"{what} {name}: a device tensor (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise L.RehrsegHipError(f"{what} {name}: float32, got {t.dtype}")
+    if input.dim() not in (4, 5) or tuple(input.shape) != tuple(target.shape):
+        raise L.RehrsegHipError(f"{what}: input and target of one shape (N, C, D, H, W) or (N, C, H, W), got "
+                                f"{tuple(input.shape)} and {tuple(target.shape)}")
+    if input.device != target.device:
+        raise L.RehrsegHipError(f"{what}: operands on one device")
+    if input.dim() == 4:
+        input, target = input.unsqueeze(2), target.unsqueeze(2)
+    weights = tuple(float(w) for w in weights)
+    if len(weights) != 4:
+        raise L.RehrsegHipError(f"{what}: four weights (l1, l2, ssim, sobel)")
+    return input, target, tuple(int(v) for v in input.shape), weights
+
+
+def _strides5(t):
+    return (C.c_int64 * 5)(*t.stride())
+
+
+def structure_loss_fwd(input, target, weights, data_range=1.0, need_grad=True):
+    """loss = l1 mean|p - t| + l2 mean (p - t)^2 + ssim (1 - mean SSIM) + sobel mean|G(p) - G(t)| of the fp32 device
+    views input / target, (N, C, D, H, W) or (N, C, H, W), read through their strides (rehr_structure_loss_fwd_f32).
+    weights = (l1, l2, ssim, sobel).  -> (loss: 0-dim float32, stats: (N, 4) float64 per-sample sums, fields: what
+    structure_loss_bwd needs of the SSIM term, or None), all on the device; nothing is read back."""
+    x, t, shape, w = _structure_loss_operands("structure_loss_fwd", input, target, weights)
+    lib = L.load()
+    nbytes = int(lib.rehr_structure_loss_workspace_bytes(*shape))
+    if nbytes < 0:
+        L.check(nbytes, "rehr_structure_loss_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    stats = torch.empty((shape[0], 4), dtype=torch.float64, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    fields = (torch.empty(shape[:3] + (3,) + shape[3:], dtype=torch.float32, device=x.device)
+              if (need_grad and w[2] != 0.0) else None)
+    L.check(lib.rehr_structure_loss_fwd_f32(_ptr(x), _strides5(x), _ptr(t), _strides5(t), *shape, *w, float(data_range),
+                                            _ptr(stats), _ptr(loss), _ptr(fields), _ptr(ws), nbytes, _stream()),
+            "rehr_structure_loss_fwd_f32")
+    return loss, stats, fields
+
+
+def structure_loss_bwd(input, target, weights, fields, grad_out, out=None):
+    """grad_out (one fp32 device element) * d loss / d input of structure_loss_fwd's loss, contiguous in input's shape
+    (or written into `out` through its strides); fields: structure_loss_fwd's for the same operands and weights."""
+    x, t, shape, w = _structure_loss_operands("structure_loss_bwd", input, target, weights)
+    for g, name in ((grad_out, "grad_out"), (fields, "fields"), (out, "out")):
+        if g is None:
+            continue
+        if not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float32:
+            raise L.RehrsegHipError(f"structure_loss_bwd {name}: a float32 device tensor")
+    if grad_out is None or grad_out.numel() != 1:
+        raise L.RehrsegHipError("structure_loss_bwd grad_out: one element")
+    if w[2] != 0.0 and (fields is None or tuple(fields.shape) != shape[:3] + (3,) + shape[3:] or not fields.is_contiguous()):
+        raise L.RehrsegHipError("structure_loss_bwd fields: structure_loss_fwd's (N, C, D, 3, H, W) tensor")
+    if out is None:
+        out = torch.empty(tuple(input.shape), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != tuple(input.shape):
+        raise L.RehrsegHipError("structure_loss_bwd out: input's shape")
+    o = out.unsqueeze(2) if out.dim() == 4 else out
+    L.check(L.load().rehr_structure_loss_bwd_f32(_ptr(x), _strides5(x), _ptr(t), _strides5(t), *shape, *w,
+                                                 _ptr(fields if w[2] != 0.0 else None), _ptr(grad_out), _ptr(o),
+                                                 _strides5(o), _stream()), "rehr_structure_loss_bwd_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- sr_head.2 on the bf16 matrix cores
 def _thin5_ws(d, dev, f32=False):
     fn = L.load().rehr_conv5_thin_f32_workspace_bytes if f32 else L.load().rehr_conv5_thin_workspace_bytes

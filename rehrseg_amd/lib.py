@@ -222,6 +222,9 @@ PROTOTYPES = {
     "rehr_sr_metrics_workspace_bytes": (_i64, [_i32] * 4),
     "rehr_sr_metrics_f32": (C.c_int, [_vp] * 8 + [_i32] * 4 + [_f32, _vp, _vp, _i64, _vp]),
     "rehr_sr_metrics_bf16": (C.c_int, [_vp] * 8 + [_i32] * 4 + [_f32, _vp, _vp, _i64, _vp]),
+    "rehr_structure_loss_workspace_bytes": (_i64, [_i32] * 5),
+    "rehr_structure_loss_fwd_f32": (C.c_int, [_vp] * 4 + [_i32] * 5 + [_f32] * 5 + [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "rehr_structure_loss_bwd_f32": (C.c_int, [_vp] * 4 + [_i32] * 5 + [_f32] * 4 + [_vp] * 5),
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),
