@@ -128,11 +128,8 @@ __global__ __launch_bounds__(kStatThreads) void stats_partial_kernel(const float
   __shared__ double red[4][kStatThreads / 64];
   s = wave_sum_d(s);
   q = wave_sum_d(q);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  }
+  mn = wave_min(mn);
+  mx = wave_max(mx);
   const int wv = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     red[0][wv] = s;

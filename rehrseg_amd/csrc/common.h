@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rehrseg_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -84,6 +85,75 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// integer counts (exact, so the order does not matter)
+template <typename T, typename = std::enable_if_t<std::is_integral<T>::value>>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Fixed-order fp64 sums of a block of kSumThreads: a butterfly per wave, the four waves' partials through LDS, then
+// ((w0 + w1) + w2) + w3.  The deterministic reductions of the metric, loss and validation kernels go through these
+// functions, so that order is written once.
+constexpr int kSumThreads = 256;
+template <int K>
+__device__ __forceinline__ double wave_order_sum(const double (*red)[K], const int k) {
+  return ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+// red[wave][k] = the wave's sum of v[k]; ends with the barrier after which every thread may read red
+template <int K>
+__device__ __forceinline__ void block_partials(double (&v)[K], double (*red)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum_d(v[k]);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wave][k] = v[k];
+  }
+  __syncthreads();
+}
+// thread k < K writes the block's sum of value k to out[k]
+template <int K>
+__device__ __forceinline__ void block_sums(double (&v)[K], double (*red)[K], double* out) {
+  block_partials(v, red);
+  if (threadIdx.x < K) out[threadIdx.x] = wave_order_sum(red, threadIdx.x);
+}
+// one block per sample: out[k] = the sum of slot k of the sample's `per` tiles in w[per][K], in a fixed order
+template <int K>
+__device__ __forceinline__ void block_sums_of_tiles(const double* __restrict__ w, const int per, double (*red)[K],
+                                                    double* out) {
+  double v[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = 0.0;
+  for (int i = threadIdx.x; i < per; i += kSumThreads) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] += w[(int64_t)i * K + k];
+  }
+  block_sums(v, red, out);
+}
+
+// Unsigned codes that order like the floats they encode: all bits of a negative flipped, the sign bit of the rest
+// (-0 < +0).  A NaN has a code but no place in the order: it must not be fed to a min / max, and a select has to
+// look for it on its own.
+__device__ __forceinline__ uint32_t ord_of_bits(uint32_t bits) {
+  return bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ uint32_t bits_of_ord(uint32_t code) {
+  return code ^ ((code >> 31) ? 0x80000000u : 0xffffffffu);
+}
+__device__ __forceinline__ uint32_t f2ord(float f) { return ord_of_bits(__float_as_uint(f)); }
+__device__ __forceinline__ float ord2f(uint32_t code) { return __uint_as_float(bits_of_ord(code)); }
 
 // 4 consecutive channels of one voxel in the activations' dtype (fp32, or bf16 on the mixed-precision path)
 __device__ __forceinline__ void store4(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }

@@ -43,9 +43,6 @@ struct RankState {
   uint32_t prefix, krem, rep, pad;
 };
 
-__device__ __forceinline__ uint32_t key_of(uint32_t bits) { return bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u); }
-__device__ __forceinline__ uint32_t bits_of(uint32_t key) { return key ^ ((key >> 31) ? 0x80000000u : 0xffffffffu); }
-
 // h[bin] += 1 for every lane with `on`; called by whole waves
 __device__ __forceinline__ void wave_count(unsigned* h, const bool on, const uint32_t bin, const int lane) {
   u64 todo = __ballot(on);
@@ -66,7 +63,7 @@ __device__ __forceinline__ void wave_count(unsigned* h, const bool on, const uin
 template <int PASS>
 __device__ __forceinline__ void count_element(unsigned* h, const bool valid, const uint32_t bits, const int R,
                                               const uint32_t* pre, const uint32_t live, const int lane, bool& nan) {
-  const uint32_t key = key_of(bits);
+  const uint32_t key = ord_of_bits(bits);
   if (PASS == 0) {
     nan = nan || (valid && (bits & 0x7fffffffu) > 0x7f800000u);
     wave_count(h, valid, key >> 24, lane);
@@ -166,7 +163,7 @@ __global__ __launch_bounds__(kBins) void select_scan_kernel(unsigned* __restrict
       if (next[r].prefix == next[t].prefix) rep = (uint32_t)r;
     sb[t] = RankState{next[t].prefix, next[t].krem, rep, 0u};
     if (pass == 3) {
-      const uint32_t bits = nanflag[b] ? 0x7fc00000u : bits_of(next[t].prefix);
+      const uint32_t bits = nanflag[b] ? 0x7fc00000u : bits_of_ord(next[t].prefix);
       out[(size_t)b * R + t] = __uint_as_float(bits);
     }
   }

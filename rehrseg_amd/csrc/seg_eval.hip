@@ -112,12 +112,6 @@ __global__ __launch_bounds__(kThreads) void tta_blend_kernel(const float* __rest
   }
 }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // V consecutive voxels per thread (V = 8: 16-byte loads and stores of the fp16 planes), grid-stride; the Dice terms
 // are reduced over the wave and added with one atomic per wave; stats[0] is set on a normalised +-inf
 template <int V>
@@ -183,9 +177,9 @@ __global__ __launch_bounds__(kThreads) void finalize_kernel(__half* __restrict__
   }
   if (inf) stats[0] = 1ull;  // plain vector store; every writer stores the same value
   if (gt != nullptr) {
-    inter = wave_sum_u64(inter);
-    sp = wave_sum_u64(sp);
-    sg = wave_sum_u64(sg);
+    inter = wave_sum(inter);
+    sp = wave_sum(sp);
+    sg = wave_sum(sg);
     if ((threadIdx.x & 63) == 0) {
       if (inter) atomicAdd(stats + 1, (unsigned long long)inter);
       if (sp) atomicAdd(stats + 2, (unsigned long long)sp);

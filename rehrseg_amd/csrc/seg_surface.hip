@@ -68,11 +68,8 @@ __global__ __launch_bounds__(kThreads) void surface_kernel(const uint8_t* __rest
     np += bits & 1;
     ng += bits >> 1;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    np += __shfl_xor(np, o, 64);
-    ng += __shfl_xor(ng, o, 64);
-  }
+  np = wave_sum(np);
+  ng = wave_sum(ng);
   if ((threadIdx.x & 63) == 0) {
     if (np) atomicAdd(counts, (unsigned long long)np);
     if (ng) atomicAdd(counts + 1, (unsigned long long)ng);
@@ -194,19 +191,19 @@ __global__ __launch_bounds__(kThreads) void edt_line_kernel(const float* __restr
   }
 }
 
-// thread 0 returns the block's sum: a butterfly per wave, then the four waves in order
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_d(v);
+// every thread returns the block's sum, in the order of common.h's block sums; the leading barrier lets `red` be
+// used again right after a call
+__device__ __forceinline__ double block_sum(double v, double (*red)[1]) {
+  double a[1] = {v};
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+  block_partials(a, red);
+  return wave_order_sum(red, 0);
 }
 
 // parts[b][f] = the sum of the finite entries of dist[f][b * 256 + t + k * kParts * 256], a fixed partition
 __global__ __launch_bounds__(kThreads) void surface_sum_kernel(const float* __restrict__ dist, const int64_t N,
                                                                double* __restrict__ parts) {
-  __shared__ double red[kThreads / 64];
+  __shared__ double red[kThreads / 64][1];
   double s0 = 0.0, s1 = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += (int64_t)kParts * kThreads) {
     const float a = dist[i], b = dist[N + i];
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void surface_finish_kernel(const double* 
                                                                   const float* __restrict__ sorted,
                                                                   const unsigned long long* __restrict__ counts,
                                                                   const int64_t N, double* __restrict__ out) {
-  __shared__ double red[kThreads / 64];
+  __shared__ double red[kThreads / 64][1];
   const double s0 = block_sum(parts[threadIdx.x * 2], red);
   const double s1 = block_sum(parts[threadIdx.x * 2 + 1], red);
   if (threadIdx.x != 0) return;

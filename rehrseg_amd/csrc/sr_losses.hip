@@ -6,9 +6,9 @@
 //   rehr_structure_loss_bwd_f32   d loss / d input in gather form: every pixel is owned by one thread.
 //
 // Operands are logical (N, C, D, H, W) images addressed through five element strides; every (H, W) slice is an image.
-// SSIM is the index of csrc/sr_metrics.hip, operation for operation (the same taps, the horizontal 11-tap pass, then
-// the vertical one, one fmaf per tap in ascending order, nothing contracted), so 1 - the SSIM term is the mean index
-// rehr_sr_metrics_f32 reports.  G is the Sobel magnitude sqrt(gx^2 + gy^2 + 1e-6) with the 3x3 kernels / 8 and
+// SSIM is the index of csrc/sr_metrics.hip by construction: both kernels run the taps, the two 11-tap passes and the
+// index of csrc/ssim_tile.h on tiles staged the same way, so 1 - the SSIM term is the mean index rehr_sr_metrics_f32
+// reports, bit for bit.  G is the Sobel magnitude sqrt(gx^2 + gy^2 + 1e-6) with the 3x3 kernels / 8 and
 // replicate padding.  The tiles are staged with CLAMPED coordinates: that is the replicate padding the Sobel term
 // needs, and the SSIM term never looks at a staged position outside the slice from a valid window.
 //
@@ -18,29 +18,18 @@
 // fields staged with a 5-pixel halo (zero outside the valid positions).  The Sobel term needs u = sign(G(p) - G(t))
 // (gx, gy) / G(p) on tile + 1, from the images on tile + 2, and gathers the 3x3 neighbours with the adjoint of the
 // replicate padding.  A weight of 0 skips its term's arithmetic, its staging included.
-#include <math.h>
-
-#include "common.h"
+#include "ssim_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 32;             // interior edge
-constexpr int kHalo = 5;
-constexpr int kRows = kTile + 2 * kHalo;   // 42 staged rows
-constexpr int kPitch = 44;            // staged row pitch in floats: 16-byte rows, columns 42 / 43 are padding
 constexpr int kSlots = 4;             // doubles per block in the workspace
 constexpr int kImg = kTile + 4;       // backward: images with a 2-pixel halo
 constexpr int kImgPitch = kImg + 1;
 constexpr int kU = kTile + 2;         // backward: the Sobel fields with a 1-pixel halo
 constexpr int kUPitch = kU + 1;
 enum { kL1 = 1, kL2 = 2, kSsim = 4, kSobel = 8 };
-
-struct GaussTaps {
-  float w[11];
-};
 
 struct View {        // a logical (N, C, D, H, W) fp32 image in element strides
   float* p;
@@ -57,22 +46,6 @@ __device__ __forceinline__ float sobel(const float* s, const int pitch, const in
   gx = (((c - a) + 2.f * (f - d)) + (k - g)) * 0.125f;
   gy = (((g - a) + 2.f * (h - b)) + (k - c)) * 0.125f;
   return sqrtf((gx * gx + gy * gy) + 1e-6f);
-}
-
-// thread t < kSlots adds the four waves' sums of value t in wave order and returns the total
-__device__ __forceinline__ void block_sums(double (&v)[kSlots], double (*red)[kSlots], double* out) {
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) v[k] = wave_sum_d(v[k]);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) red[wave][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kSlots) {
-    const int k = threadIdx.x;
-    out[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
 }
 
 // blockIdx.x -> tile origin and the slice's index (n * C + c) * D + d
@@ -144,71 +117,20 @@ __global__ __launch_bounds__(kThreads) void structure_loss_fwd_kernel(const View
   }
 
   if (flags & kSsim) {
-    // horizontal pass: 4 neighbouring outputs per item from 16 staged columns (four 16-byte LDS reads per image)
-    for (int i = threadIdx.x; i < kRows * (kTile / 4); i += kThreads) {
-      const int r = i >> 3, q = (i & 7) * 4;
-      float xs[16], ys[16];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(&sP[r * kPitch + q + 4 * v]);
-        const f32x4 c = *reinterpret_cast<const f32x4*>(&sT[r * kPitch + q + 4 * v]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          xs[4 * v + e] = a[e];
-          ys[4 * v + e] = c[e];
-        }
-      }
-      f32x4 f[5];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        float ax = 0.f, ay = 0.f, axx = 0.f, ayy = 0.f, axy = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-          const float x = xs[o + k], y = ys[o + k];
-          ax = fmaf(g.w[k], x, ax);
-          ay = fmaf(g.w[k], y, ay);
-          axx = fmaf(g.w[k], x * x, axx);
-          ayy = fmaf(g.w[k], y * y, ayy);
-          axy = fmaf(g.w[k], x * y, axy);
-        }
-        f[0][o] = ax;
-        f[1][o] = ay;
-        f[2][o] = axx;
-        f[3][o] = ayy;
-        f[4][o] = axy;
-      }
-#pragma unroll
-      for (int k = 0; k < 5; ++k) *reinterpret_cast<f32x4*>(&sF[k][r * kTile + q]) = f[k];
-    }
+    // the window moments of x, y, x^2, y^2, xy: horizontal pass, barrier, vertical pass (ssim_tile.h)
+    ssim_hpass_pair(g, sP, sT, sF);
     __syncthreads();
 
-    // vertical pass: column c, 4 neighbouring rows per thread from 14 rows of every field
-    const int c = threadIdx.x & 31, r0 = (threadIdx.x >> 5) * 4;
     float m[5][4];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      float col[14];
-#pragma unroll
-      for (int j = 0; j < 14; ++j) col[j] = sF[k][(r0 + j) * kTile + c];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) a = fmaf(g.w[j], col[o + j], a);
-        m[k][o] = a;
-      }
-    }
-    const int x = x0 + c;
+    ssim_vpass<5>(g, sF, m);
+    const int x = x0 + ssim_column();
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      const int y = y0 + r0 + o;
-      if (y >= kHalo && y < H - kHalo && x >= kHalo && x < W - kHalo) {
+      const int y = y0 + ssim_row0() + o;
+      ssim_if_valid(y, x, H, W, [&] {
         const float mx = m[0][o], my = m[1][o];
-        const float mxx = mx * mx, myy = my * my, mxy = mx * my;
-        const float sxx = m[2][o] - mxx, syy = m[3][o] - myy, sxy = m[4][o] - mxy;
-        const float A1 = 2.f * mxy + C1, A2 = 2.f * sxy + C2;
-        const float B1 = (mxx + myy) + C1, B2 = (sxx + syy) + C2;
-        const float S = (A1 * A2) / (B1 * B2);
+        const SsimIndex ix = ssim_index(mx, my, m[2][o], m[3][o], m[4][o], C1, C2);
+        const float A1 = ix.A1, A2 = ix.A2, B1 = ix.B1, B2 = ix.B2, S = ix.S;
         s_ssim += (double)S;
         if (fields != nullptr) {
           const float inv = 1.f / (B1 * B2);
@@ -218,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void structure_loss_fwd_kernel(const View
           f[plane] = -S / B2;
           f[2 * plane] = (2.f * A1) * inv;
         }
-      }
+      });
     }
   }
 
@@ -230,13 +152,7 @@ __global__ __launch_bounds__(kThreads) void structure_loss_fwd_kernel(const View
 __global__ __launch_bounds__(kThreads) void structure_loss_finish_kernel(const double* __restrict__ ws, const int per,
                                                                          double* __restrict__ stats) {
   __shared__ double sRed[kThreads / 64][kSlots];
-  const double* w = ws + (int64_t)blockIdx.x * per * kSlots;
-  double v[kSlots] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < per; i += kThreads) {
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) v[k] += w[(int64_t)i * kSlots + k];
-  }
-  block_sums(v, sRed, stats + (int64_t)blockIdx.x * kSlots);
+  block_sums_of_tiles(ws + (int64_t)blockIdx.x * per * kSlots, per, sRed, stats + (int64_t)blockIdx.x * kSlots);
 }
 
 // the weighted loss from the samples' sums, in sample order
@@ -313,8 +229,7 @@ __global__ __launch_bounds__(kThreads) void structure_loss_bwd_kernel(const View
       const int r = j / kPitch, c = j - r * kPitch;
       const int y = y0 - kHalo + r, x = x0 - kHalo + c;
       float v = 0.f;
-      if (c < kRows && y >= kHalo && y < H - kHalo && x >= kHalo && x < W - kHalo)
-        v = fields[(img * 3 + k) * plane + (int64_t)y * W + x];
+      if (c < kRows) ssim_if_valid(y, x, H, W, [&] { v = fields[(img * 3 + k) * plane + (int64_t)y * W + x]; });
       sA[k][j] = v;
     }
   }
@@ -339,50 +254,15 @@ __global__ __launch_bounds__(kThreads) void structure_loss_bwd_kernel(const View
       sU[1][r * kUPitch + c] = uy;
     }
   }
-  if (flags & kSsim) {   // horizontal pass over the three fields, as the forward's
-    for (int i = threadIdx.x; i < kRows * (kTile / 4); i += kThreads) {
-      const int r = i >> 3, q = (i & 7) * 4;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        float xs[16];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const f32x4 a = *reinterpret_cast<const f32x4*>(&sA[k][r * kPitch + q + 4 * v]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) xs[4 * v + e] = a[e];
-        }
-        f32x4 f;
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-          float a = 0.f;
-#pragma unroll
-          for (int t = 0; t < 11; ++t) a = fmaf(g.w[t], xs[o + t], a);
-          f[o] = a;
-        }
-        *reinterpret_cast<f32x4*>(&sH[k][r * kTile + q]) = f;
-      }
-    }
+  if (flags & kSsim) {   // horizontal pass over the three fields, the forward's
+    ssim_hpass_plain<3>(g, sA, sH);
   }
   __syncthreads();
 
-  const int c = threadIdx.x & 31, r0 = (threadIdx.x >> 5) * 4;
+  const int c = ssim_column(), r0 = ssim_row0();
   const int x = x0 + c;
   float m[3][4];
-  if (flags & kSsim) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      float col[14];
-#pragma unroll
-      for (int j = 0; j < 14; ++j) col[j] = sH[k][(r0 + j) * kTile + c];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) a = fmaf(g.w[j], col[o + j], a);
-        m[k][o] = a;
-      }
-    }
-  }
+  if (flags & kSsim) ssim_vpass<3>(g, sH, m);
   const float go = *grad_out;
   float xs_[3], xd_[3];
   if (flags & kSobel) adjoint_taps(x, W, xs_, xd_);
@@ -414,23 +294,6 @@ __global__ __launch_bounds__(kThreads) void structure_loss_bwd_kernel(const View
   }
 }
 
-struct Geometry {
-  int tiles_x, tiles_y;
-  int64_t per, blocks;
-};
-
-int geometry(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, Geometry* g) {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return REHR_EINVAL;
-  g->tiles_x = (W + kTile - 1) / kTile;
-  g->tiles_y = (H + kTile - 1) / kTile;
-  g->per = (int64_t)g->tiles_y * g->tiles_x;
-  if (g->per > INT32_MAX / D || g->per * D > INT32_MAX / C) return REHR_ENOSUP;
-  g->per *= (int64_t)D * C;
-  if (g->per > INT32_MAX / N) return REHR_ENOSUP;   // one 1-D grid
-  g->blocks = g->per * N;
-  return REHR_OK;
-}
-
 // the terms with a weight other than 0; < 0: a weight that is no finite number
 int term_flags(float l1, float l2, float ssim, float sobel) {
   if (!isfinite(l1) || !isfinite(l2) || !isfinite(ssim) || !isfinite(sobel)) return -1;
@@ -445,22 +308,11 @@ int view(const float* p, const int64_t* s, View* v) {
   return REHR_OK;
 }
 
-GaussTaps gauss_taps() {
-  GaussTaps taps;
-  double e[11], sum = 0.0;
-  for (int k = 0; k < 11; ++k) {
-    e[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-    sum += e[k];
-  }
-  for (int k = 0; k < 11; ++k) taps.w[k] = (float)(e[k] / sum);
-  return taps;
-}
-
 }  // namespace
 
 extern "C" int64_t rehr_structure_loss_workspace_bytes(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W) {
   Geometry g;
-  const int rc = geometry(N, C, D, H, W, &g);
+  const int rc = tile_geometry(N, C, D, H, W, false, &g);
   return rc != REHR_OK ? rc : g.blocks * kSlots * (int64_t)sizeof(double);
 }
 
@@ -476,9 +328,8 @@ extern "C" int rehr_structure_loss_fwd_f32(const float* input, const int64_t* in
   const int flags = term_flags(l1, l2, ssim, sobel);
   if (flags < 0) return REHR_EINVAL;
   Geometry g;
-  const int rc = geometry(N, C, D, H, W, &g);
+  const int rc = tile_geometry(N, C, D, H, W, (flags & kSsim) != 0, &g);
   if (rc != REHR_OK) return rc;
-  if ((flags & kSsim) && (H < 11 || W < 11)) return REHR_ENOSUP;
   if (workspace_bytes < g.blocks * kSlots * (int64_t)sizeof(double)) return REHR_EINVAL;
   if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(stats)) & 7) return REHR_EINVAL;
   if ((reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(fields)) & 3) return REHR_EINVAL;
@@ -509,9 +360,8 @@ extern "C" int rehr_structure_loss_bwd_f32(const float* input, const int64_t* in
   const int flags = term_flags(l1, l2, ssim, sobel);
   if (flags < 0) return REHR_EINVAL;
   Geometry g;
-  const int rc = geometry(N, C, D, H, W, &g);
+  const int rc = tile_geometry(N, C, D, H, W, (flags & kSsim) != 0, &g);
   if (rc != REHR_OK) return rc;
-  if ((flags & kSsim) && (H < 11 || W < 11)) return REHR_ENOSUP;
   if ((flags & kSsim) && fields == nullptr) return REHR_EINVAL;
   if ((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(grad_output)) & 3) return REHR_EINVAL;
   // every pixel of d input is written by one thread: its strides must address N * C * D * H * W distinct elements

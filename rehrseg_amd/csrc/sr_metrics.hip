@@ -11,47 +11,22 @@
 // whose window lies inside the slice.
 //
 // One block per 32x32 tile of one slice.  Both images are staged in LDS with a 5-pixel halo (42x42, read once from
-// HBM apart from the halo), a horizontal 11-tap pass writes the five fields x, y, x^2, y^2, xy to LDS, a vertical pass
-// forms the window moments and the index.  L1, MSE and the counts come from the tile's own 32x32 interior while it is
-// staged, so every voxel counts once.  Per-voxel terms and window moments are fp32, every sum across voxels, positions
-// or blocks is fp64: the block's sums go to its own slot of the workspace and a second kernel adds the slots of a
-// sample in a fixed order -- no floating-point atomics, the same bits on every run.  x^2, y^2 and xy go through the
-// same operations, and nothing below is contracted behind the source's back, so p == t gives an index of exactly 1.
-#include "common.h"
+// HBM apart from the halo); the horizontal 11-tap pass over the five fields x, y, x^2, y^2, xy, the vertical pass that
+// forms the window moments and the index itself are csrc/ssim_tile.h, the code the structure loss runs as well.  L1,
+// MSE and the counts come from the tile's own 32x32 interior while it is staged, so every voxel counts once.
+// Per-voxel terms and window moments are fp32, every sum across voxels, positions or blocks is fp64: the block's sums
+// go to its own slot of the workspace and a second kernel adds the slots of a sample in a fixed order -- no
+// floating-point atomics, the same bits on every run.
+#include "ssim_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 32;             // interior edge
-constexpr int kHalo = 5;
-constexpr int kRows = kTile + 2 * kHalo;   // 42 staged rows
-constexpr int kPitch = 44;            // staged row pitch in floats: 16-byte rows, columns 42 / 43 are zero padding
 constexpr int kSlots = 6;             // doubles per block in the workspace
-
-struct GaussTaps {
-  float w[11];
-};
 
 __device__ __forceinline__ float ld(const float* p) { return *p; }
 __device__ __forceinline__ float ld(const __bf16* p) { return (float)*p; }
-
-// thread t < kSlots adds the four waves' sums of value t in wave order and returns the total
-__device__ __forceinline__ void block_sums(double (&v)[kSlots], double (*red)[kSlots], double* out) {
-#pragma unroll
-  for (int k = 0; k < kSlots; ++k) v[k] = wave_sum_d(v[k]);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) red[wave][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kSlots) {
-    const int k = threadIdx.x;
-    out[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
-}
 
 template <typename P>
 __global__ __launch_bounds__(kThreads) void sr_metrics_tile_kernel(
@@ -106,73 +81,19 @@ __global__ __launch_bounds__(kThreads) void sr_metrics_tile_kernel(
   }
   __syncthreads();
 
-  // horizontal pass: 4 neighbouring outputs per item from 16 staged columns (four 16-byte LDS reads per image)
-  for (int i = threadIdx.x; i < kRows * (kTile / 4); i += kThreads) {
-    const int r = i >> 3, q = (i & 7) * 4;
-    float xs[16], ys[16];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(&sP[r * kPitch + q + 4 * v]);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(&sT[r * kPitch + q + 4 * v]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        xs[4 * v + e] = a[e];
-        ys[4 * v + e] = c[e];
-      }
-    }
-    f32x4 f[5];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      float ax = 0.f, ay = 0.f, axx = 0.f, ayy = 0.f, axy = 0.f;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const float x = xs[o + k], y = ys[o + k];
-        ax = fmaf(g.w[k], x, ax);
-        ay = fmaf(g.w[k], y, ay);
-        axx = fmaf(g.w[k], x * x, axx);
-        ayy = fmaf(g.w[k], y * y, ayy);
-        axy = fmaf(g.w[k], x * y, axy);
-      }
-      f[0][o] = ax;
-      f[1][o] = ay;
-      f[2][o] = axx;
-      f[3][o] = ayy;
-      f[4][o] = axy;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) *reinterpret_cast<f32x4*>(&sF[k][r * kTile + q]) = f[k];
-  }
+  // the window moments of x, y, x^2, y^2, xy: horizontal pass, barrier, vertical pass (ssim_tile.h)
+  ssim_hpass_pair(g, sP, sT, sF);
   __syncthreads();
 
-  // vertical pass: column c, 4 neighbouring rows per thread from 14 rows of every field
   {
-    const int c = threadIdx.x & 31, r0 = (threadIdx.x >> 5) * 4;
     float m[5][4];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      float col[14];
-#pragma unroll
-      for (int j = 0; j < 14; ++j) col[j] = sF[k][(r0 + j) * kTile + c];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) a = fmaf(g.w[j], col[o + j], a);
-        m[k][o] = a;
-      }
-    }
-    const int x = x0 + c;
+    ssim_vpass<5>(g, sF, m);
+    const int x = x0 + ssim_column();
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      const int y = y0 + r0 + o;
-      if (y >= kHalo && y < H - kHalo && x >= kHalo && x < W - kHalo) {
-        const float mx = m[0][o], my = m[1][o];
-        const float mxx = mx * mx, myy = my * my, mxy = mx * my;
-        const float sxx = m[2][o] - mxx, syy = m[3][o] - myy, sxy = m[4][o] - mxy;
-        const float num = (2.f * mxy + C1) * (2.f * sxy + C2);
-        const float den = ((mxx + myy) + C1) * ((sxx + syy) + C2);
-        s_ssim += (double)(num / den);
-      }
+      ssim_if_valid(y0 + ssim_row0() + o, x, H, W, [&] {
+        s_ssim += (double)ssim_index(m[0][o], m[1][o], m[2][o], m[3][o], m[4][o], C1, C2).S;
+      });
     }
   }
 
@@ -186,34 +107,12 @@ __global__ __launch_bounds__(kThreads) void sr_metrics_finish_kernel(const doubl
                                                                      double* __restrict__ stats) {
   __shared__ double sRed[kThreads / 64][kSlots];
   __shared__ double sOut[kSlots];
-  const double* w = ws + (int64_t)blockIdx.x * per * kSlots;
-  double v[kSlots] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < per; i += kThreads) {
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) v[k] += w[(int64_t)i * kSlots + k];
-  }
-  block_sums(v, sRed, sOut);
+  block_sums_of_tiles(ws + (int64_t)blockIdx.x * per * kSlots, per, sRed, sOut);
   __syncthreads();
   if (threadIdx.x < 7) {
     const int k = threadIdx.x;
     stats[blockIdx.x * 7 + k] = k < 3 ? sOut[k] : (k == 3 ? ssim_cnt : sOut[k - 1]);
   }
-}
-
-struct Geometry {
-  int tiles_x, tiles_y;
-  int64_t per, blocks;
-};
-
-int geometry(int32_t N, int32_t D, int32_t H, int32_t W, Geometry* g) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return REHR_EINVAL;
-  if (H < 11 || W < 11) return REHR_ENOSUP;
-  g->tiles_x = (W + kTile - 1) / kTile;
-  g->tiles_y = (H + kTile - 1) / kTile;
-  g->per = (int64_t)D * g->tiles_y * g->tiles_x;
-  if (g->per > INT32_MAX / N) return REHR_ENOSUP;   // one 1-D grid
-  g->blocks = g->per * N;
-  return REHR_OK;
 }
 
 template <typename P>
@@ -226,7 +125,7 @@ int sr_metrics(const P* pred, const int64_t* ps, const float* tgt, const int64_t
   if (slog != nullptr && (ls == nullptr || gs == nullptr)) return REHR_EINVAL;
   if (!(data_range > 0.f)) return REHR_EINVAL;
   Geometry g;
-  const int rc = geometry(N, D, H, W, &g);
+  const int rc = tile_geometry(N, 1, D, H, W, true, &g);
   if (rc != REHR_OK) return rc;
   if (workspace_bytes < g.blocks * kSlots * (int64_t)sizeof(double)) return REHR_EINVAL;
   if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(stats)) & 7) return REHR_EINVAL;
@@ -234,17 +133,10 @@ int sr_metrics(const P* pred, const int64_t* ps, const float* tgt, const int64_t
   if (slog == nullptr) ls = gs = zero;
   for (int a = 0; a < 4; ++a)
     if (ps[a] < 0 || ts[a] < 0 || ls[a] < 0 || gs[a] < 0) return REHR_EINVAL;
-  GaussTaps taps;
-  double e[11], sum = 0.0;
-  for (int k = 0; k < 11; ++k) {
-    e[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-    sum += e[k];
-  }
-  for (int k = 0; k < 11; ++k) taps.w[k] = (float)(e[k] / sum);
   const float c1 = 0.01f * data_range, c2 = 0.03f * data_range;
   hipLaunchKernelGGL(sr_metrics_tile_kernel<P>, dim3((unsigned)g.blocks), dim3(kThreads), 0, (hipStream_t)stream, pred,
                      ps[0], ps[1], ps[2], ps[3], tgt, ts[0], ts[1], ts[2], ts[3], slog, ls[0], ls[1], ls[2], ls[3], stgt,
-                     gs[0], gs[1], gs[2], gs[3], D, H, W, g.tiles_x, g.tiles_y, c1 * c1, c2 * c2, taps,
+                     gs[0], gs[1], gs[2], gs[3], D, H, W, g.tiles_x, g.tiles_y, c1 * c1, c2 * c2, gauss_taps(),
                      (double*)workspace);
   hipLaunchKernelGGL(sr_metrics_finish_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream,
                      (const double*)workspace, (int)g.per, (double)D * (double)(H - 10) * (double)(W - 10), stats);
@@ -256,7 +148,7 @@ int sr_metrics(const P* pred, const int64_t* ps, const float* tgt, const int64_t
 
 extern "C" int64_t rehr_sr_metrics_workspace_bytes(int32_t N, int32_t D, int32_t H, int32_t W) {
   Geometry g;
-  const int rc = geometry(N, D, H, W, &g);
+  const int rc = tile_geometry(N, 1, D, H, W, true, &g);
   return rc != REHR_OK ? rc : g.blocks * kSlots * (int64_t)sizeof(double);
 }
 

@@ -28,26 +28,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTile = 64;
 
-// unsigned codes that order like the floats they encode (-0 < +0; NaN is not ordered and must not be fed)
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t c) {
-  return __uint_as_float((c & 0x80000000u) ? (c & 0x7fffffffu) : ~c);
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // wave reduction, then the block's 4 partials through LDS, then one atomic pair per block
 __device__ __forceinline__ void block_minmax_commit(float lo, float hi, uint32_t* __restrict__ mm) {
   __shared__ float s_lo[kThreads / 64], s_hi[kThreads / 64];

@@ -32,6 +32,23 @@ def _window(f, g):
     return v
 
 
+def _ssim_index(p, t, data_range):
+    """The window means mu_x, mu_y, the four factors and the index S = (A1 A2) / (B1 B2) on the valid positions of the
+    last two axes, fp32: the statement of csrc/ssim_tile.h's ssim_index."""
+    g = _taps()
+    c1, c2 = np.float32(0.01) * np.float32(data_range), np.float32(0.03) * np.float32(data_range)
+    C1, C2 = c1 * c1, c2 * c2
+    mx, my, exx, eyy, exy = (_window(f, g) for f in (p, t, p * p, t * t, p * t))
+    mxx, myy, mxy = mx * mx, my * my, mx * my
+    sxx, syy, sxy = exx - mxx, eyy - myy, exy - mxy
+    two = np.float32(2.0)
+    A1, A2 = two * mxy + C1, two * sxy + C2
+    B1, B2 = (mxx + myy) + C1, (sxx + syy) + C2
+    S = (A1 * A2) / (B1 * B2)
+    assert S.dtype == np.float32
+    return mx, my, A1, A2, B1, B2, S
+
+
 def sr_metrics(pred, target, seg_logits=None, seg_target=None, data_range=1.0):
     if pred.dtype not in (torch.float32, torch.bfloat16) or target.dtype != torch.float32:
         raise TypeError("pred: float32 or bfloat16 (widened at the load), target: float32")
@@ -41,16 +58,7 @@ def sr_metrics(pred, target, seg_logits=None, seg_target=None, data_range=1.0):
     e = p - t
     out[:, 0] = np.abs(e).astype(np.float64).sum((1, 2, 3))
     out[:, 1] = (e * e).astype(np.float64).sum((1, 2, 3))
-    g = _taps()
-    c1, c2 = np.float32(0.01) * np.float32(data_range), np.float32(0.03) * np.float32(data_range)
-    C1, C2 = c1 * c1, c2 * c2
-    mx, my, exx, eyy, exy = (_window(f, g) for f in (p, t, p * p, t * t, p * t))
-    mxx, myy, mxy = mx * mx, my * my, mx * my
-    sxx, syy, sxy = exx - mxx, eyy - myy, exy - mxy
-    two = np.float32(2.0)
-    S = ((two * mxy + C1) * (two * sxy + C2)) / (((mxx + myy) + C1) * ((sxx + syy) + C2))
-    assert S.dtype == np.float32
-    out[:, 2] = S.astype(np.float64).sum((1, 2, 3))
+    out[:, 2] = _ssim_index(p, t, data_range)[-1].astype(np.float64).sum((1, 2, 3))
     out[:, 3] = D * (H - 10) * (W - 10)
     if seg_logits is not None:
         fp, ft = seg_logits.float().numpy() > 0, seg_target.numpy() > 0.5

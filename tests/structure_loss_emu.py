@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 import emu_backend
-from sr_metrics_emu import _taps, _window
+from sr_metrics_emu import _ssim_index, _taps
 
 name = "structure_loss_emu"
 F32 = np.float32
@@ -47,16 +47,8 @@ def _sobel(f):
 
 def _ssim_fields(p, t, data_range):
     """S and the coefficient fields a = dS/dmu_x, b = dS/dE[x^2], c = dS/dE[xy] on the valid positions, fp32."""
-    g = _taps()
-    c1, c2 = F32(0.01) * F32(data_range), F32(0.03) * F32(data_range)
-    C1, C2 = c1 * c1, c2 * c2
-    mx, my, exx, eyy, exy = (_window(f, g) for f in (p, t, p * p, t * t, p * t))
-    mxx, myy, mxy = mx * mx, my * my, mx * my
-    sxx, syy, sxy = exx - mxx, eyy - myy, exy - mxy
+    mx, my, A1, A2, B1, B2, S = _ssim_index(p, t, data_range)
     two, one = F32(2), F32(1)
-    A1, A2 = two * mxy + C1, two * sxy + C2
-    B1, B2 = (mxx + myy) + C1, (sxx + syy) + C2
-    S = (A1 * A2) / (B1 * B2)
     inv = one / (B1 * B2)
     a = (two * my) * (A2 - A1) * inv - (two * mx) * S * (one / B1 - one / B2)
     b = -S / B2

@@ -131,6 +131,13 @@ def test_one_minus_the_ssim_term_is_sr_metrics_ssim(kind):
     assert abs((1.0 - float(loss)) - float(ssim64.mean())) <= max(4 * d32, sc.SSIM_FLOOR)
     # the per-sample sums are sr_metrics' own, bit for bit
     assert torch.equal(stats[:, 2].view(torch.int64), hb.sr_metrics(x[:, 0], y[:, 0], data_range=rng)[:, 2].view(torch.int64))
+    # and at every single-channel shape of the cases: one window position, a tile edge with both halos, three tiles
+    for s in (s for s in lc.SHAPES if s[1] == 1):
+        p, t, rng = lc.make_case(kind, s)
+        x, y = _dev(p, t)
+        _, stats, _ = hb.structure_loss_fwd(x, y, (0.0, 0.0, 1.0, 0.0), rng, need_grad=False)
+        assert torch.equal(stats[:, 2].view(torch.int64),
+                           hb.sr_metrics(x[:, 0], y[:, 0], data_range=rng)[:, 2].view(torch.int64)), s
 
 
 @pytest.mark.parametrize("kind", lc.KINDS)
