@@ -8,6 +8,7 @@
 // over a block's rows in registers + LDS, and finish with one double atomic per
 // channel per block.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -587,7 +588,6 @@ __global__ void transpose_cs_kernel(const float* __restrict__ x, float* __restri
   }
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // blocks for a per-sample column reduction: cover S rows with <= ~1024 blocks/sample
 inline int64_t rows_per_block_for(int64_t S, int C, int N) {
   const int rpp = EW_THREADS / (C / 4);
@@ -646,7 +646,7 @@ extern "C" int rehr_se_gate_bwd_f32(const double* dgate_acc, const float* gate, 
 
 extern "C" int rehr_upsample_depth_fwd_f32(const float* x, float* y, int32_t N, int32_t Di, int32_t Do,
                                            int64_t HW, int32_t C, void* stream) {
-  if (!x || !y || N < 1 || Di < 1 || Do < 1 || HW < 1 || C < 4 || C % 4 || !aligned16(x) || !aligned16(y))
+  if (!x || !y || N < 1 || Di < 1 || Do < 1 || HW < 1 || C < 4 || C % 4 || misaligned(16, x, y))
     return REHR_EINVAL;
   const int64_t total = (int64_t)N * Do * HW * C / 4;
   hipLaunchKernelGGL(upsample_depth_fwd_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, x, y, N,
@@ -656,8 +656,7 @@ extern "C" int rehr_upsample_depth_fwd_f32(const float* x, float* y, int32_t N, 
 }
 extern "C" int rehr_upsample_depth_bwd_f32(const float* dy, float* dx, int32_t N, int32_t Di, int32_t Do,
                                            int64_t HW, int32_t C, void* stream) {
-  if (!dy || !dx || N < 1 || Di < 1 || Do < 1 || HW < 1 || C < 4 || C % 4 || !aligned16(dy) ||
-      !aligned16(dx))
+  if (!dy || !dx || N < 1 || Di < 1 || Do < 1 || HW < 1 || C < 4 || C % 4 || misaligned(16, dy, dx))
     return REHR_EINVAL;
   const int64_t total = (int64_t)N * Di * HW * C / 4;
   hipLaunchKernelGGL(upsample_depth_bwd_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, dy, dx,
@@ -671,7 +670,7 @@ template <typename TG, typename TY>
 int upmix_depth_fwd_t(const TG* g, const float* bias, TY* y, int32_t N, int32_t Di, int32_t Do, int64_t HW, int32_t C,
                       int32_t KD, int32_t pd, int32_t act, float slope, void* stream) {
   if (!g || !y || N < 1 || Di < 1 || Do < 1 || HW < 1 || C < 4 || C % 4 || KD < 1 || pd < 0 || pd >= KD ||
-      !aligned16(g) || !aligned16(y) || (bias && !aligned16(bias)) || KD > UPMIX_MAXKD)
+      misaligned(16, g, y, bias) || KD > UPMIX_MAXKD)
     return REHR_EINVAL;
   const int64_t total = (int64_t)N * ((Do + UPMIX_RUN - 1) / UPMIX_RUN) * HW * C / 4;
   hipLaunchKernelGGL((upmix_depth_fwd_kernel<TG, TY>), dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, g, bias, y, N, Di,
@@ -683,7 +682,7 @@ template <typename TG, typename TY>
 int upmix_depth_bwd_t(const TY* dz, const TY* y, TG* dg, int32_t N, int32_t Di, int32_t Do, int64_t HW, int32_t C,
                       int32_t KD, int32_t pd, int32_t act, float slope, void* stream) {
   if (!dz || !dg || N < 1 || Di < 1 || Do < 1 || HW < 1 || C < 4 || C % 4 || KD < 1 || pd < 0 || pd >= KD ||
-      !aligned16(dz) || !aligned16(dg) || (y && !aligned16(y)))
+      misaligned(16, dz, dg, y))
     return REHR_EINVAL;
   const int64_t total = (int64_t)N * HW * C / 4;   // one thread per (sample, voxel column, channel quad)
   hipLaunchKernelGGL((upmix_depth_bwd_kernel<TG, TY>), dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, dz,
@@ -694,8 +693,8 @@ int upmix_depth_bwd_t(const TY* dz, const TY* y, TG* dg, int32_t N, int32_t Di, 
 template <typename T>
 int channel_sum_actgrad_t(const T* dy, const T* y, int32_t ld, int64_t rows, int32_t C, int32_t act, float slope,
                           float* out, double* scratch, void* stream) {
-  if (!dy || !y || !out || !scratch || rows < 1 || C < 4 || C % 4 || C > 1024 || ld % 4 || !aligned16(dy) ||
-      !aligned16(y))
+  if (!dy || !y || !out || !scratch || rows < 1 || C < 4 || C % 4 || C > 1024 || ld % 4 ||
+      misaligned(16, dy, y))
     return REHR_EINVAL;
   if (hipMemsetAsync(scratch, 0, sizeof(double) * C, ST) != hipSuccess) return REHR_EHIP;
   const int64_t rpb = rows_per_block_for(rows, C, 1);
@@ -745,7 +744,7 @@ extern "C" int rehr_window_stem_assemble_f32(const float* g0, const float* g1, c
                                              const float* bias, float* y, int32_t B, int32_t nwin, int32_t nslices,
                                              int64_t HW, int32_t C, int32_t act, float slope, void* stream) {
   if (!g0 || !g1 || !g2 || !mean || !y || B < 1 || nwin < 1 || nslices != nwin + 3 || HW < 1 || C < 4 || C % 4 ||
-      !aligned16(g0) || !aligned16(g1) || !aligned16(g2) || !aligned16(y) || (bias && !aligned16(bias)))
+      misaligned(16, g0, g1, g2, y, bias))
     return REHR_EINVAL;
   const int64_t total = (int64_t)B * nwin * 4 * HW * C / 4;
   hipLaunchKernelGGL(window_stem_assemble_kernel<float>, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, g0, g1, g2, mean,
@@ -758,7 +757,7 @@ extern "C" int rehr_window_stem_assemble_bf16(const float* g0, const float* g1, 
                                               const float* bias, void* y, int32_t B, int32_t nwin, int32_t nslices,
                                               int64_t HW, int32_t C, int32_t act, float slope, void* stream) {
   if (!g0 || !g1 || !g2 || !mean || !y || B < 1 || nwin < 1 || nslices != nwin + 3 || HW < 1 || C < 4 || C % 4 ||
-      !aligned16(g0) || !aligned16(g1) || !aligned16(g2) || (((uintptr_t)y) & 7) || (bias && !aligned16(bias)))
+      misaligned(16, g0, g1, g2, bias) || misaligned(8, y))
     return REHR_EINVAL;
   const int64_t total = (int64_t)B * nwin * 4 * HW * C / 4;
   hipLaunchKernelGGL(window_stem_assemble_kernel<__bf16>, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ST, g0, g1, g2, mean,
@@ -810,7 +809,7 @@ extern "C" int rehr_cosdist_bwd_f32(const float* x1, const float* x2, const doub
 
 extern "C" int rehr_act_fwd_f32(const float* x, float* y, int64_t n, int32_t act, float slope,
                                 void* stream) {
-  if (!x || !y || n < 4 || n % 4 || !aligned16(x) || !aligned16(y)) return REHR_EINVAL;
+  if (!x || !y || n < 4 || n % 4 || misaligned(16, x, y)) return REHR_EINVAL;
   hipLaunchKernelGGL(act_fwd_kernel, dim3(ew_blocks(n / 4)), dim3(EW_THREADS), 0, ST, x, y, n / 4, act,
                      slope);
   REHR_LAUNCH_CHECK();
@@ -823,7 +822,7 @@ extern "C" int rehr_channel_sum_actgrad_bf16(const void* dy, const void* y, int3
 
 extern "C" int rehr_copy_channels_f32(const float* x, int32_t ldx, float* y, int32_t ldy, int64_t rows,
                                       int32_t C, void* stream) {
-  if (!x || !y || rows < 1 || C < 4 || C % 4 || ldx % 4 || ldy % 4 || !aligned16(x) || !aligned16(y))
+  if (!x || !y || rows < 1 || C < 4 || C % 4 || ldx % 4 || ldy % 4 || misaligned(16, x, y))
     return REHR_EINVAL;
   hipLaunchKernelGGL(copy_channels_kernel, dim3(ew_blocks(rows * (C / 4))), dim3(EW_THREADS), 0, ST, x,
                      ldx, y, ldy, rows, C);
@@ -909,7 +908,7 @@ extern "C" int rehr_sum_slabs_stats_f32(const float* slabs, int32_t S, int64_t s
   if (!slabs || !y || !stats || S < 1 || N < 1 || N > 65535 || SV < 1 || C < 4 || C % 4 || C > 1024 ||
       slab_stride < (int64_t)N * SV * C || slab_stride % 4)
     return REHR_EINVAL;
-  if ((((uintptr_t)slabs) | ((uintptr_t)y)) & 15) return REHR_EINVAL;
+  if (misaligned(16, slabs, y)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(SV, C, N);
   const int blocks = (int)((SV + rpb - 1) / rpb);
   hipLaunchKernelGGL(sum_slabs_stats_kernel<float>, dim3(blocks, N), dim3(EW_THREADS), 0, (hipStream_t)stream, slabs, S,
@@ -924,7 +923,7 @@ extern "C" int rehr_sum_slabs_stats_bf16(const float* slabs, int32_t S, int64_t 
   if (!slabs || !y || !stats || S < 1 || N < 1 || N > 65535 || SV < 1 || C < 4 || C % 4 || C > 1024 ||
       slab_stride < (int64_t)N * SV * C || slab_stride % 4)
     return REHR_EINVAL;
-  if ((((uintptr_t)slabs) & 15) || (((uintptr_t)y) & 7)) return REHR_EINVAL;
+  if (misaligned(16, slabs) || misaligned(8, y)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(SV, C, N);
   const int blocks = (int)((SV + rpb - 1) / rpb);
   hipLaunchKernelGGL(sum_slabs_stats_kernel<__bf16>, dim3(blocks, N), dim3(EW_THREADS), 0, (hipStream_t)stream, slabs, S,
@@ -936,7 +935,7 @@ extern "C" int rehr_sum_slabs_stats_bf16(const float* slabs, int32_t S, int64_t 
 extern "C" int rehr_sum_slabs_bias_act_bf16(const float* slabs, int32_t S, int64_t slab_stride, const float* bias,
                                             void* y, int64_t rows, int32_t C, int32_t act, float slope, void* stream) {
   if (!slabs || !y || S < 1 || rows < 1 || C < 4 || C % 4 || slab_stride < rows * C || slab_stride % 4) return REHR_EINVAL;
-  if ((((uintptr_t)slabs) & 15) || (((uintptr_t)y) & 7)) return REHR_EINVAL;
+  if (misaligned(16, slabs) || misaligned(8, y)) return REHR_EINVAL;
   hipLaunchKernelGGL(sum_slabs_bias_act_kernel<__bf16>, dim3(ew_blocks(rows * (C / 4))), dim3(EW_THREADS), 0,
                      (hipStream_t)stream, slabs, S, slab_stride, bias, (__bf16*)y, rows, C, act, slope);
   REHR_LAUNCH_CHECK();
@@ -947,7 +946,7 @@ extern "C" int rehr_sum_slabs_bias_act_f32(const float* slabs, int32_t S, int64_
                                            float* y, int64_t rows, int32_t C, int32_t act, float slope,
                                            void* stream) {
   if (!slabs || !y || S < 1 || rows < 1 || C < 4 || C % 4 || slab_stride < rows * C || slab_stride % 4) return REHR_EINVAL;
-  if ((((uintptr_t)slabs) | ((uintptr_t)y)) & 15) return REHR_EINVAL;
+  if (misaligned(16, slabs, y)) return REHR_EINVAL;
   hipLaunchKernelGGL(sum_slabs_bias_act_kernel<float>, dim3(ew_blocks(rows * (C / 4))), dim3(EW_THREADS), 0,
                      (hipStream_t)stream, slabs, S, slab_stride, bias, y, rows, C, act, slope);
   REHR_LAUNCH_CHECK();

@@ -20,6 +20,7 @@
 // to one LDS word, whose cost on this chip is unmeasured: up to kPeel times the lanes that share the first pending
 // lane's bin are folded by a ballot into one add of their number, and only what is left goes out lane by lane.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -232,24 +233,29 @@ __global__ __launch_bounds__(kThreads) void intensity_apply_kernel(const float* 
   }
 }
 
-inline int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
-
 int check_select(int32_t B, int32_t R) {
   if (B < 1 || R < 1) return REHR_EINVAL;
   if (B > 65535 || R > kMaxRanks) return REHR_ENOSUP;
   return REHR_OK;
 }
 
-inline int64_t state_bytes(int32_t B, int32_t R) { return align16((int64_t)B * R * (int64_t)sizeof(RankState)); }
-inline int64_t flag_bytes(int32_t B) { return align16((int64_t)B * 4); }
+// workspace: [RankState per (item, rank)][NaN flag per item][counts: B * R * 256 uint32]
+struct Layout {
+  RankState* state;
+  unsigned *nanflag, *hist;
+  int64_t bytes;
+};
+Layout layout(void* base, int64_t B, int64_t R) {
+  Carver c(base);   // a braced list is evaluated left to right
+  return {c.take<RankState>(B * R), c.take<unsigned>(B), c.take<unsigned>(B * R * kBins), c.bytes()};
+}
 
 }  // namespace
 
-// workspace: [RankState per (item, rank)][NaN flag per item][counts: B * R * 256 uint32]
 extern "C" int64_t rehr_order_stats_workspace_bytes(int32_t B, int32_t R) {
   const int rc = check_select(B, R);
   if (rc != REHR_OK) return rc;
-  return state_bytes(B, R) + flag_bytes(B) + (int64_t)B * R * kBins * 4;
+  return layout(nullptr, B, R).bytes;
 }
 
 extern "C" int rehr_order_stats_f32(const float* x, int32_t B, int64_t S, int64_t item_stride, const int64_t* ranks,
@@ -264,21 +270,13 @@ extern "C" int rehr_order_stats_f32(const float* x, int32_t B, int64_t S, int64_
     if (ranks[r] < 0 || ranks[r] >= S) return REHR_EINVAL;
     rk.k[r] = (uint32_t)ranks[r];
   }
-  const int64_t need = rehr_order_stats_workspace_bytes(B, R);
-  if (workspace_bytes < need) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 3))
-    return REHR_EINVAL;
-  char* ws = static_cast<char*>(workspace);
-  RankState* state = reinterpret_cast<RankState*>(ws);
-  unsigned* nanflag = reinterpret_cast<unsigned*>(ws + state_bytes(B, R));
-  unsigned* hist = reinterpret_cast<unsigned*>(ws + state_bytes(B, R) + flag_bytes(B));
+  const auto [state, nanflag, hist, need] = layout(workspace, B, R);
+  if (workspace_bytes < need || misaligned(16, workspace) || misaligned(4, x, out)) return REHR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n16 = need / 16, zg = (n16 + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(select_zero_kernel, dim3((unsigned)(zg < 4096 ? zg : 4096)), dim3(kThreads), 0, st,
-                     reinterpret_cast<uint4*>(ws), n16);
-  int64_t blocks = (S / 4 + kVecPerBlock - 1) / kVecPerBlock;
-  blocks = blocks < 1 ? 1 : blocks > kMaxBlocks ? kMaxBlocks : blocks;
-  const dim3 grid((unsigned)blocks, (unsigned)B), scan((unsigned)B);
+  const int64_t n16 = need / 16;
+  hipLaunchKernelGGL(select_zero_kernel, dim3(grid_for(n16, kThreads, 4096)), dim3(kThreads), 0, st,
+                     static_cast<uint4*>(workspace), n16);
+  const dim3 grid(grid_for(S / 4, kVecPerBlock, kMaxBlocks), (unsigned)B), scan((unsigned)B);
   hipLaunchKernelGGL(select_hist_kernel<0>, grid, dim3(kThreads), 0, st, x, S, item_stride, R,
                      (const RankState*)state, hist, nanflag);
   hipLaunchKernelGGL(select_scan_kernel, scan, dim3(kBins), 0, st, hist, state, R, 0, rk, (const unsigned*)nanflag, out);
@@ -299,7 +297,7 @@ extern "C" int rehr_percentile_f64(const float* stats, int32_t B, int32_t Q, con
                                    double* out, void* stream) {
   if (stats == nullptr || t == nullptr || out == nullptr || B < 1 || Q < 1) return REHR_EINVAL;
   if (Q > REHR_PERCENTILE_MAX_Q) return REHR_ENOSUP;
-  if ((reinterpret_cast<uintptr_t>(stats) & 3) || (reinterpret_cast<uintptr_t>(out) & 7)) return REHR_EINVAL;
+  if (misaligned(4, stats) || misaligned(8, out)) return REHR_EINVAL;
   Lerp lerp = {};
   for (int j = 0; j < Q; ++j) {
     if (!(t[j] >= 0.0 && t[j] < 1.0)) return REHR_EINVAL;
@@ -318,11 +316,8 @@ extern "C" int rehr_intensity_apply_f32(const float* x, float* y, int32_t B, int
   if (mode != REHR_INTENSITY_PERCENTILE && mode != REHR_INTENSITY_ZEROONE) return REHR_EINVAL;
   if (bounds_stride < 2 || (B > 1 && (x_stride < S || y_stride < S))) return REHR_EINVAL;
   if (B > 65535 || S > kMaxS) return REHR_ENOSUP;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 3) || (reinterpret_cast<uintptr_t>(bounds) & 7))
-    return REHR_EINVAL;
-  int64_t blocks = (S / 4 + kThreads * 4 - 1) / (kThreads * 4);
-  blocks = blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks;
-  hipLaunchKernelGGL(intensity_apply_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(kThreads), 0,
+  if (misaligned(4, x, y) || misaligned(8, bounds)) return REHR_EINVAL;
+  hipLaunchKernelGGL(intensity_apply_kernel, dim3(grid_for(S / 4, kThreads * 4, 2048), (unsigned)B), dim3(kThreads), 0,
                      (hipStream_t)stream, x, y, S, x_stride, y_stride, mode == REHR_INTENSITY_PERCENTILE, bounds,
                      bounds_stride);
   REHR_LAUNCH_CHECK();

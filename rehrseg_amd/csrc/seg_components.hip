@@ -30,6 +30,7 @@
 // wave; the largest component is an atomicMax of (size << 32) | (0xffffffff - root), which prefers the smaller root
 // among equal sizes.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -324,21 +325,25 @@ int check_extent(int32_t D, int32_t H, int32_t W) {
   return REHR_OK;
 }
 
-inline int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
-
-inline unsigned grid_for(int64_t n, int per_block) {
-  const int64_t g = (n + per_block - 1) / per_block;
-  return (unsigned)(g < kMaxBlocks ? (g < 1 ? 1 : g) : kMaxBlocks);
+// workspace: [64 bytes: the two packed keys][sizes of pred's components: N uint32][gt voxels inside them: N]
+//            [sizes of gt's components: N][their hit flags: N], every array indexed by root
+struct Layout {
+  u64* keys;
+  unsigned *sizeP, *ovP, *sizeG, *hitG;
+  int64_t bytes;
+};
+Layout layout(void* base, int64_t N) {
+  Carver c(base);   // a braced list is evaluated left to right
+  return {c.take<u64>(kHeaderBytes / 8), c.take<unsigned>(N), c.take<unsigned>(N), c.take<unsigned>(N),
+          c.take<unsigned>(N), c.bytes()};
 }
 
 }  // namespace
 
-// workspace: [64 bytes: the two packed keys][sizes of pred's components: N uint32][gt voxels inside them: N]
-//            [sizes of gt's components: N][their hit flags: N], every array indexed by root
 extern "C" int64_t rehr_seg_cc_workspace_bytes(int32_t D, int32_t H, int32_t W) {
   const int rc = check_extent(D, H, W);
   if (rc != REHR_OK) return rc;
-  return kHeaderBytes + 4 * align16((int64_t)D * H * W * (int64_t)sizeof(unsigned));
+  return layout(nullptr, (int64_t)D * H * W).bytes;
 }
 
 extern "C" int rehr_seg_cc_roots_i32(const uint8_t* mask, int32_t D, int32_t H, int32_t W, int32_t connectivity,
@@ -347,13 +352,13 @@ extern "C" int rehr_seg_cc_roots_i32(const uint8_t* mask, int32_t D, int32_t H, 
   if (connectivity != 6 && connectivity != 18 && connectivity != 26) return REHR_EINVAL;
   const int rc = check_extent(D, H, W);
   if (rc != REHR_OK) return rc;
-  if (workspace_bytes < rehr_seg_cc_workspace_bytes(D, H, W)) return REHR_EINVAL;
-  if (reinterpret_cast<uintptr_t>(roots) & 3) return REHR_EINVAL;
   const int64_t rows = (int64_t)D * H;
+  if (workspace_bytes < layout(workspace, rows * W).bytes || misaligned(4, roots)) return REHR_EINVAL;
   const int N = (int)(rows * W);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cc_init_kernel, dim3(grid_for(rows, kWaves)), dim3(kThreads), 0, st, mask, rows, W, roots);
-  const dim3 grid(grid_for(N, kThreads));
+  hipLaunchKernelGGL(cc_init_kernel, dim3(grid_for(rows, kWaves, kMaxBlocks)), dim3(kThreads), 0, st, mask, rows, W,
+                     roots);
+  const dim3 grid(grid_for(N, kThreads, kMaxBlocks));
   if (connectivity == 6)
     hipLaunchKernelGGL(cc_merge_kernel<1>, grid, dim3(kThreads), 0, st, mask, D, H, W, roots);
   else if (connectivity == 18)
@@ -370,25 +375,17 @@ extern "C" int rehr_seg_cc_lesion_i64(const int32_t* roots_pred, const int32_t* 
                                       void* workspace, int64_t workspace_bytes, void* stream) {
   if (roots_pred == nullptr || roots_gt == nullptr || out == nullptr || workspace == nullptr) return REHR_EINVAL;
   if (N < 1 || N > kMaxVoxels) return REHR_ENOSUP;
-  const int64_t arr = align16(N * (int64_t)sizeof(unsigned)), need = kHeaderBytes + 4 * arr;
+  const auto [keys, sizeP, ovP, sizeG, hitG, need] = layout(workspace, N);
   if (workspace_bytes < need) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(out) & 7) ||
-      ((reinterpret_cast<uintptr_t>(roots_pred) | reinterpret_cast<uintptr_t>(roots_gt)) & 3))
-    return REHR_EINVAL;
-  char* ws = static_cast<char*>(workspace);
-  u64* keys = reinterpret_cast<u64*>(ws);
-  unsigned* sizeP = reinterpret_cast<unsigned*>(ws + kHeaderBytes);
-  unsigned* ovP = reinterpret_cast<unsigned*>(ws + kHeaderBytes + arr);
-  unsigned* sizeG = reinterpret_cast<unsigned*>(ws + kHeaderBytes + 2 * arr);
-  unsigned* hitG = reinterpret_cast<unsigned*>(ws + kHeaderBytes + 3 * arr);
+  if (misaligned(16, workspace) || misaligned(8, out) || misaligned(4, roots_pred, roots_gt)) return REHR_EINVAL;
   u64* o = reinterpret_cast<u64*>(out);
   hipStream_t st = (hipStream_t)stream;
   const int n = (int)N;
-  hipLaunchKernelGGL(cc_zero_kernel, dim3(grid_for(need / 16, kThreads)), dim3(kThreads), 0, st,
-                     reinterpret_cast<uint4*>(ws), need / 16);
+  hipLaunchKernelGGL(cc_zero_kernel, dim3(grid_for(need / 16, kThreads, kMaxBlocks)), dim3(kThreads), 0, st,
+                     static_cast<uint4*>(workspace), need / 16);
   // a wave takes at least 8 consecutive steps of 64 voxels where there are that many; at most 1024 blocks
   const int64_t steps = (N + 63) / 64;
-  const unsigned blocks = grid_for(steps, kWaves * 8) < 1024 ? grid_for(steps, kWaves * 8) : 1024;
+  const unsigned blocks = grid_for(steps, kWaves * 8, 1024);
   const int per_wave = (int)((steps + (int64_t)blocks * kWaves - 1) / ((int64_t)blocks * kWaves));
   hipLaunchKernelGGL(cc_stats_kernel, dim3(blocks), dim3(kThreads), 0, st, roots_pred, roots_gt, n, per_wave, sizeP, ovP,
                      sizeG, hitG, o);
@@ -404,12 +401,9 @@ extern "C" int rehr_seg_cc_compact_i32(const int32_t* roots, int64_t N, const in
                                        int64_t* count, void* stream) {
   if (roots == nullptr || rank == nullptr || labels == nullptr || count == nullptr) return REHR_EINVAL;
   if (N < 1 || N > kMaxVoxels) return REHR_ENOSUP;
-  if (((reinterpret_cast<uintptr_t>(roots) | reinterpret_cast<uintptr_t>(rank) | reinterpret_cast<uintptr_t>(labels)) &
-       3) ||
-      (reinterpret_cast<uintptr_t>(count) & 7))
-    return REHR_EINVAL;
-  hipLaunchKernelGGL(cc_compact_kernel, dim3(grid_for(N, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, roots,
-                     (int)N, rank, labels, reinterpret_cast<u64*>(count));
+  if (misaligned(4, roots, rank, labels) || misaligned(8, count)) return REHR_EINVAL;
+  hipLaunchKernelGGL(cc_compact_kernel, dim3(grid_for(N, kThreads, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream,
+                     roots, (int)N, rank, labels, reinterpret_cast<u64*>(count));
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }

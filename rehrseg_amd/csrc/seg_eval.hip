@@ -19,6 +19,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "host_util.h"
 
 #pragma clang fp contract(off)
 
@@ -188,11 +189,6 @@ __global__ __launch_bounds__(kThreads) void finalize_kernel(__half* __restrict__
   }
 }
 
-inline unsigned grid_for(int64_t n, int64_t cap) {
-  int64_t b = (n + kThreads - 1) / kThreads;
-  return (unsigned)(b < 1 ? 1 : (b < cap ? b : cap));
-}
-
 }  // namespace
 
 extern "C" int rehr_tta_gather_f32(const float* vol, float* out, int32_t D, int32_t H, int32_t W, int32_t pad_d,
@@ -205,7 +201,7 @@ extern "C" int rehr_tta_gather_f32(const float* vol, float* out, int32_t D, int3
   // the padded volume needs no further check here
   if ((int64_t)d * h * w * 8 >= ((int64_t)1 << 40)) return REHR_EINVAL;
   const int64_t n = (int64_t)d * h * ((w + 3) / 4);
-  const unsigned g = grid_for(n, 8192);
+  const unsigned g = grid_for(n, kThreads, 8192);
   const int z0 = start_d - pad_d, y0 = start_h - pad_h, x0 = start_w - pad_w;
   if (w % 4 == 0)
     hipLaunchKernelGGL(tta_gather_kernel<true>, dim3(g), dim3(kThreads), 0, (hipStream_t)stream, vol, out, D, H, W,
@@ -226,7 +222,7 @@ extern "C" int rehr_tta_blend_f16acc(const float* pred, const int64_t* strides, 
   for (int a = 0; a < 5; ++a)
     if (strides[a] < 0) return REHR_EINVAL;
   const int64_t n = (int64_t)d * h * w;
-  hipLaunchKernelGGL(tta_blend_kernel, dim3(grid_for(n, 8192)), dim3(kThreads), 0, (hipStream_t)stream, pred,
+  hipLaunchKernelGGL(tta_blend_kernel, dim3(grid_for(n, kThreads, 8192)), dim3(kThreads), 0, (hipStream_t)stream, pred,
                      strides[0], strides[1], strides[2], strides[3], strides[4], C, d, h, w,
                      (const __half*)gaussian, (__half*)logits, (__half*)counts, Do, Ho, Wo, od, oh, ow);
   REHR_LAUNCH_CHECK();
@@ -242,16 +238,16 @@ extern "C" int rehr_seg_eval_finalize_f16(void* logits, const void* counts, int3
   if (crop_d < 0 || crop_h < 0 || crop_w < 0 || crop_d + CD > D || crop_h + CH > H || crop_w + CW > W)
     return REHR_EINVAL;
   if (gt != nullptr && labels == nullptr) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(counts)) & 1) return REHR_EINVAL;
+  if (misaligned(2, logits, counts)) return REHR_EINVAL;
   const int64_t N = (int64_t)D * H * W;
-  const bool vec = N % 8 == 0 && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(counts)) & 15) == 0;
+  const bool vec = N % 8 == 0 && !misaligned(16, logits, counts);
   unsigned long long* st = reinterpret_cast<unsigned long long*>(stats);
   if (vec)
-    hipLaunchKernelGGL(finalize_kernel<8>, dim3(grid_for(N / 8, 2048)), dim3(kThreads), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(finalize_kernel<8>, dim3(grid_for(N / 8, kThreads, 2048)), dim3(kThreads), 0, (hipStream_t)stream,
                        (__half*)logits, (const __half*)counts, D, H, W, crop_d, crop_h, crop_w, CD, CH, CW, labels, gt,
                        st);
   else
-    hipLaunchKernelGGL(finalize_kernel<1>, dim3(grid_for(N, 2048)), dim3(kThreads), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(finalize_kernel<1>, dim3(grid_for(N, kThreads, 2048)), dim3(kThreads), 0, (hipStream_t)stream,
                        (__half*)logits, (const __half*)counts, D, H, W, crop_d, crop_h, crop_w, CD, CH, CW, labels, gt,
                        st);
   REHR_LAUNCH_CHECK();

@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_util.h"
 
 #pragma clang fp contract(off)
 
@@ -251,18 +252,26 @@ int check_extent(int32_t D, int32_t H, int32_t W) {
   return REHR_OK;
 }
 
-inline int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
-
 inline bool good_spacing(float s) { return s > 0.f && s < INFINITY; }   // false for NaN
+
+// workspace: [256 x 2 doubles of the sum][field pair A: 2N floats][field pair B: 2N floats][surface bits: N bytes]
+struct Layout {
+  double* parts;
+  float *A, *B;
+  uint8_t* surf;
+  int64_t bytes;
+};
+Layout layout(void* base, int64_t N) {
+  Carver c(base);   // a braced list is evaluated left to right
+  return {c.take<double>(kParts * 2), c.take<float>(2 * N), c.take<float>(2 * N), c.take<uint8_t>(N), c.bytes()};
+}
 
 }  // namespace
 
-// workspace: [256 x 2 doubles of the sum][field pair A: 2N floats][field pair B: 2N floats][surface bits: N bytes]
 extern "C" int64_t rehr_seg_surface_workspace_bytes(int32_t D, int32_t H, int32_t W) {
   const int rc = check_extent(D, H, W);
   if (rc != REHR_OK) return rc;
-  const int64_t N = (int64_t)D * H * W;
-  return kPartsBytes + 2 * align16(2 * N * (int64_t)sizeof(float)) + align16(N);
+  return layout(nullptr, (int64_t)D * H * W).bytes;
 }
 
 extern "C" int rehr_seg_surface_dist_f32(const uint8_t* pred, const uint8_t* gt, int32_t D, int32_t H, int32_t W,
@@ -273,21 +282,14 @@ extern "C" int rehr_seg_surface_dist_f32(const uint8_t* pred, const uint8_t* gt,
   const int rc = check_extent(D, H, W);
   if (rc != REHR_OK) return rc;
   if (!good_spacing(sd) || !good_spacing(sh) || !good_spacing(sw)) return REHR_EINVAL;
-  if (workspace_bytes < rehr_seg_surface_workspace_bytes(D, H, W)) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(dist) & 3) ||
-      (reinterpret_cast<uintptr_t>(counts) & 7))
-    return REHR_EINVAL;
   const int64_t N = (int64_t)D * H * W, HW = (int64_t)H * W;
-  const int64_t pair = align16(2 * N * (int64_t)sizeof(float));
-  char* ws = static_cast<char*>(workspace);
-  float* A = reinterpret_cast<float*>(ws + kPartsBytes);
-  float* B = reinterpret_cast<float*>(ws + kPartsBytes + pair);
-  uint8_t* surf = reinterpret_cast<uint8_t*>(ws + kPartsBytes + 2 * pair);
+  const auto [parts, A, B, surf, need] = layout(workspace, N);
+  if (workspace_bytes < need) return REHR_EINVAL;
+  if (misaligned(16, workspace) || misaligned(4, dist) || misaligned(8, counts)) return REHR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
 
-  int64_t g = (N + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(surface_kernel, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(kThreads), 0, st, pred, gt, D, H, W,
-                     surf, reinterpret_cast<unsigned long long*>(counts));
+  hipLaunchKernelGGL(surface_kernel, dim3(grid_for(N, kThreads, 4096)), dim3(kThreads), 0, st, pred, gt, D, H, W, surf,
+                     reinterpret_cast<unsigned long long*>(counts));
   // every grid below is at most 2^23 blocks: axes <= 2048 and N <= 2^30
   const int64_t rows = (int64_t)D * H;
   const int xtiles = (W + kLanes - 1) / kLanes;
@@ -316,11 +318,8 @@ extern "C" int rehr_seg_surface_reduce_f64(const float* dist, const float* sorte
   if (N < 1) return REHR_EINVAL;
   if (N > kMaxVoxels) return REHR_ENOSUP;
   if (workspace_bytes < kPartsBytes) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 7) || (reinterpret_cast<uintptr_t>(out) & 7) ||
-      (reinterpret_cast<uintptr_t>(counts) & 7) ||
-      ((reinterpret_cast<uintptr_t>(dist) | reinterpret_cast<uintptr_t>(sorted)) & 3))
-    return REHR_EINVAL;
-  double* parts = static_cast<double*>(workspace);
+  if (misaligned(8, workspace, out, counts) || misaligned(4, dist, sorted)) return REHR_EINVAL;
+  double* parts = static_cast<double*>(workspace);   // a buffer of its own will do: kPartsBytes on a multiple of 8
   hipLaunchKernelGGL(surface_sum_kernel, dim3(kParts), dim3(kThreads), 0, (hipStream_t)stream, dist, N, parts);
   hipLaunchKernelGGL(surface_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const double*)parts,
                      sorted, reinterpret_cast<const unsigned long long*>(counts), N, out);

@@ -313,7 +313,7 @@ int view(const float* p, const int64_t* s, View* v) {
 extern "C" int64_t rehr_structure_loss_workspace_bytes(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W) {
   Geometry g;
   const int rc = tile_geometry(N, C, D, H, W, false, &g);
-  return rc != REHR_OK ? rc : g.blocks * kSlots * (int64_t)sizeof(double);
+  return rc != REHR_OK ? rc : tile_sums_layout<kSlots>(nullptr, g).bytes;
 }
 
 extern "C" int rehr_structure_loss_fwd_f32(const float* input, const int64_t* input_strides, const float* target,
@@ -330,17 +330,16 @@ extern "C" int rehr_structure_loss_fwd_f32(const float* input, const int64_t* in
   Geometry g;
   const int rc = tile_geometry(N, C, D, H, W, (flags & kSsim) != 0, &g);
   if (rc != REHR_OK) return rc;
-  if (workspace_bytes < g.blocks * kSlots * (int64_t)sizeof(double)) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(stats)) & 7) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(fields)) & 3) return REHR_EINVAL;
+  const auto [slots, need] = tile_sums_layout<kSlots>(workspace, g);
+  if (workspace_bytes < need || misaligned(8, workspace, stats) || misaligned(4, loss, fields)) return REHR_EINVAL;
   const double V = (double)N * C * D * H * W;
   const double M = (double)N * C * D * ((double)H - 10.0) * ((double)W - 10.0);
   const float c1 = 0.01f * data_range, c2 = 0.03f * data_range;
   hipLaunchKernelGGL(structure_loss_fwd_kernel, dim3((unsigned)g.blocks), dim3(kThreads), 0, (hipStream_t)stream, in, tg,
                      C, D, H, W, g.tiles_x, g.tiles_y, flags, c1 * c1, c2 * c2, gauss_taps(),
-                     (flags & kSsim) ? fields : nullptr, (double*)workspace);
+                     (flags & kSsim) ? fields : nullptr, slots);
   hipLaunchKernelGGL(structure_loss_finish_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream,
-                     (const double*)workspace, (int)g.per, stats);
+                     (const double*)slots, (int)g.per, stats);
   hipLaunchKernelGGL(structure_loss_value_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)stats, N,
                      flags, (double)l1 / V, (double)l2 / V, (double)ssim, M, (double)sobel / V, loss);
   REHR_LAUNCH_CHECK();
@@ -363,7 +362,7 @@ extern "C" int rehr_structure_loss_bwd_f32(const float* input, const int64_t* in
   const int rc = tile_geometry(N, C, D, H, W, (flags & kSsim) != 0, &g);
   if (rc != REHR_OK) return rc;
   if ((flags & kSsim) && fields == nullptr) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(grad_output)) & 3) return REHR_EINVAL;
+  if (misaligned(4, fields, grad_output)) return REHR_EINVAL;
   // every pixel of d input is written by one thread: its strides must address N * C * D * H * W distinct elements
   const int64_t ext[5] = {N, C, D, H, W};
   for (int a = 0; a < 5; ++a)

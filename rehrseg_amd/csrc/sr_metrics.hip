@@ -127,8 +127,8 @@ int sr_metrics(const P* pred, const int64_t* ps, const float* tgt, const int64_t
   Geometry g;
   const int rc = tile_geometry(N, 1, D, H, W, true, &g);
   if (rc != REHR_OK) return rc;
-  if (workspace_bytes < g.blocks * kSlots * (int64_t)sizeof(double)) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(stats)) & 7) return REHR_EINVAL;
+  const auto [slots, need] = tile_sums_layout<kSlots>(workspace, g);
+  if (workspace_bytes < need || misaligned(8, workspace, stats)) return REHR_EINVAL;
   static const int64_t zero[4] = {0, 0, 0, 0};
   if (slog == nullptr) ls = gs = zero;
   for (int a = 0; a < 4; ++a)
@@ -136,10 +136,9 @@ int sr_metrics(const P* pred, const int64_t* ps, const float* tgt, const int64_t
   const float c1 = 0.01f * data_range, c2 = 0.03f * data_range;
   hipLaunchKernelGGL(sr_metrics_tile_kernel<P>, dim3((unsigned)g.blocks), dim3(kThreads), 0, (hipStream_t)stream, pred,
                      ps[0], ps[1], ps[2], ps[3], tgt, ts[0], ts[1], ts[2], ts[3], slog, ls[0], ls[1], ls[2], ls[3], stgt,
-                     gs[0], gs[1], gs[2], gs[3], D, H, W, g.tiles_x, g.tiles_y, c1 * c1, c2 * c2, gauss_taps(),
-                     (double*)workspace);
+                     gs[0], gs[1], gs[2], gs[3], D, H, W, g.tiles_x, g.tiles_y, c1 * c1, c2 * c2, gauss_taps(), slots);
   hipLaunchKernelGGL(sr_metrics_finish_kernel, dim3((unsigned)N), dim3(kThreads), 0, (hipStream_t)stream,
-                     (const double*)workspace, (int)g.per, (double)D * (double)(H - 10) * (double)(W - 10), stats);
+                     (const double*)slots, (int)g.per, (double)D * (double)(H - 10) * (double)(W - 10), stats);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }
@@ -149,7 +148,7 @@ int sr_metrics(const P* pred, const int64_t* ps, const float* tgt, const int64_t
 extern "C" int64_t rehr_sr_metrics_workspace_bytes(int32_t N, int32_t D, int32_t H, int32_t W) {
   Geometry g;
   const int rc = tile_geometry(N, 1, D, H, W, true, &g);
-  return rc != REHR_OK ? rc : g.blocks * kSlots * (int64_t)sizeof(double);
+  return rc != REHR_OK ? rc : tile_sums_layout<kSlots>(nullptr, g).bytes;
 }
 
 extern "C" int rehr_sr_metrics_f32(const float* pred, const int64_t* pred_strides, const float* target,
@@ -168,7 +167,7 @@ extern "C" int rehr_sr_metrics_bf16(const void* pred, const int64_t* pred_stride
                                     const int64_t* seg_target_strides, int32_t N, int32_t D, int32_t H, int32_t W,
                                     float data_range, double* stats, void* workspace, int64_t workspace_bytes,
                                     void* stream) {
-  if ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(seg_logits)) & 1) return REHR_EINVAL;
+  if (misaligned(2, pred, seg_logits)) return REHR_EINVAL;
   return sr_metrics<__bf16>((const __bf16*)pred, pred_strides, target, target_strides, (const __bf16*)seg_logits,
                             seg_logits_strides, seg_target, seg_target_strides, N, D, H, W, data_range, stats, workspace,
                             workspace_bytes, stream);

@@ -20,6 +20,7 @@
 // operators: contract(off) governs those, while the __f*_rn helpers are inlined from a header compiled with
 // contraction allowed and would be fused into v_fma.
 #include "common.h"
+#include "host_util.h"
 
 #pragma clang fp contract(off)
 
@@ -260,24 +261,16 @@ __global__ __launch_bounds__(kThreads) void unc_u8_kernel(const float* __restric
   }
 }
 
-inline unsigned grid_for(int64_t n, int64_t cap) {
-  int64_t b = (n + kThreads - 1) / kThreads;
-  return (unsigned)(b < 1 ? 1 : (b < cap ? b : cap));
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int rehr_minmax_f32(const float* x, int64_t n, uint32_t* minmax, void* stream) {
-  if (x == nullptr || minmax == nullptr || n < 1) return REHR_EINVAL;
-  if (reinterpret_cast<uintptr_t>(x) & 3) return REHR_EINVAL;
-  if (aligned16(x))
-    hipLaunchKernelGGL(minmax_kernel<true>, dim3(grid_for(n / 4 + 1, 2048)), dim3(kThreads), 0, (hipStream_t)stream, x, n,
-                       minmax);
+  if (x == nullptr || minmax == nullptr || n < 1 || misaligned(4, x)) return REHR_EINVAL;
+  if (!misaligned(16, x))
+    hipLaunchKernelGGL(minmax_kernel<true>, dim3(grid_for(n / 4 + 1, kThreads, 2048)), dim3(kThreads), 0,
+                       (hipStream_t)stream, x, n, minmax);
   else
-    hipLaunchKernelGGL(minmax_kernel<false>, dim3(grid_for(n, 2048)), dim3(kThreads), 0, (hipStream_t)stream, x, n,
-                       minmax);
+    hipLaunchKernelGGL(minmax_kernel<false>, dim3(grid_for(n, kThreads, 2048)), dim3(kThreads), 0, (hipStream_t)stream,
+                       x, n, minmax);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }
@@ -288,17 +281,17 @@ extern "C" int rehr_sr_window_gather_f32(const float* vol, float* out, int32_t X
   if (X < 1 || Y < 1 || Z < 2 || (C != 1 && C != 2)) return REHR_EINVAL;
   if (w0 < 0 || b < 1 || (int64_t)w0 + b > Z - 1) return REHR_EINVAL;
   if (Xp < X || Yp < Y || Xp % 16 || Yp % 16) return REHR_EINVAL;
-  if (!aligned16(out) || (reinterpret_cast<uintptr_t>(vol) & 3)) return REHR_EINVAL;
+  if (misaligned(16, out) || misaligned(4, vol)) return REHR_EINVAL;
   if ((int64_t)X * Y * Z * C >= ((int64_t)1 << 40) || (int64_t)b * 4 * Xp * Yp * C >= ((int64_t)1 << 40))
     return REHR_EINVAL;
   const int zoff = Z == 2 ? -2 : -1;  // the two-slice volume's single window is padded in front (:116-118)
   const int64_t n = (int64_t)b * 4 * Xp * Yp * C / 4;
   if (C == 1)
-    hipLaunchKernelGGL(window_gather_kernel<1>, dim3(grid_for(n, 16384)), dim3(kThreads), 0, (hipStream_t)stream, vol,
-                       out, X, Y, Z, w0, zoff, b, Xp, Yp);
+    hipLaunchKernelGGL(window_gather_kernel<1>, dim3(grid_for(n, kThreads, 16384)), dim3(kThreads), 0,
+                       (hipStream_t)stream, vol, out, X, Y, Z, w0, zoff, b, Xp, Yp);
   else
-    hipLaunchKernelGGL(window_gather_kernel<2>, dim3(grid_for(n, 16384)), dim3(kThreads), 0, (hipStream_t)stream, vol,
-                       out, X, Y, Z, w0, zoff, b, Xp, Yp);
+    hipLaunchKernelGGL(window_gather_kernel<2>, dim3(grid_for(n, kThreads, 16384)), dim3(kThreads), 0,
+                       (hipStream_t)stream, vol, out, X, Y, Z, w0, zoff, b, Xp, Yp);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }
@@ -313,14 +306,14 @@ extern "C" int rehr_sr_volume_scatter_f32(const float* net, const int64_t* strid
   if (seg != nullptr && C < 2) return REHR_EINVAL;
   for (int a = 0; a < 5; ++a)
     if (strides[a] < 0) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(net) | reinterpret_cast<uintptr_t>(img)) & 3) return REHR_EINVAL;
+  if (misaligned(4, net, img)) return REHR_EINVAL;
   if ((int64_t)n_windows * n_out * X * Y >= ((int64_t)1 << 40)) return REHR_EINVAL;
   const int tiles_x = (X + kTile - 1) / kTile, tiles_y = (Y + kTile - 1) / kTile;
   const int64_t blocks = (int64_t)b * n_out * tiles_x * tiles_y;
   if (blocks > 0x7fffffff) return REHR_EINVAL;
   // the vector stores need 16-byte rows: X % 4 == 0 and an aligned base; otherwise the kernel's scalar path runs, which
   // it selects by X % 4 alone, so a misaligned base with X % 4 == 0 is refused here
-  if (X % 4 == 0 && (!aligned16(img) || (seg != nullptr && (reinterpret_cast<uintptr_t>(seg) & 3)))) return REHR_EINVAL;
+  if (X % 4 == 0 && (misaligned(16, img) || misaligned(4, seg))) return REHR_EINVAL;
   hipLaunchKernelGGL(volume_scatter_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, net,
                      strides[0], strides[1], strides[2], strides[3], strides[4], n_out, X, Y, w0, in_minmax, img, seg,
                      out_minmax, tiles_x, tiles_y);
@@ -333,8 +326,8 @@ extern "C" int rehr_stage2_prep_f32(const float* img, const uint32_t* minmax, co
   if (img == nullptr || minmax == nullptr || taps == nullptr || out == nullptr) return REHR_EINVAL;
   if (L < 1 || X < 1 || P < 1 || X * P >= ((int64_t)1 << 40)) return REHR_EINVAL;
   if (L > 32) return REHR_ENOSUP;
-  if (img == out || ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(out)) & 3)) return REHR_EINVAL;
-  const bool vec = P % 4 == 0 && aligned16(img) && aligned16(out);
+  if (img == out || misaligned(4, img, out)) return REHR_EINVAL;
+  const bool vec = P % 4 == 0 && !misaligned(16, img, out);
   const int chunk = X < 64 ? X : 64;  // every chunk re-reads L - 1 rows of its neighbours
   const dim3 grid((unsigned)(((P + 3) / 4 + kThreads - 1) / kThreads), (unsigned)((X + chunk - 1) / chunk));
   if (grid.y > 65535) return REHR_ENOSUP;
@@ -359,14 +352,13 @@ extern "C" int rehr_stage2_prep_f32(const float* img, const uint32_t* minmax, co
 }
 
 extern "C" int rehr_stage2_unc_u8_f32(const float* u, const uint32_t* minmax, uint8_t* out, int64_t n, void* stream) {
-  if (u == nullptr || minmax == nullptr || out == nullptr || n < 1) return REHR_EINVAL;
-  if (reinterpret_cast<uintptr_t>(u) & 3) return REHR_EINVAL;
-  if (aligned16(u) && (reinterpret_cast<uintptr_t>(out) & 3) == 0)
-    hipLaunchKernelGGL(unc_u8_kernel<true>, dim3(grid_for(n / 4 + 1, 4096)), dim3(kThreads), 0, (hipStream_t)stream, u,
-                       minmax, out, n);
+  if (u == nullptr || minmax == nullptr || out == nullptr || n < 1 || misaligned(4, u)) return REHR_EINVAL;
+  if (!misaligned(16, u) && !misaligned(4, out))
+    hipLaunchKernelGGL(unc_u8_kernel<true>, dim3(grid_for(n / 4 + 1, kThreads, 4096)), dim3(kThreads), 0,
+                       (hipStream_t)stream, u, minmax, out, n);
   else
-    hipLaunchKernelGGL(unc_u8_kernel<false>, dim3(grid_for(n, 4096)), dim3(kThreads), 0, (hipStream_t)stream, u, minmax,
-                       out, n);
+    hipLaunchKernelGGL(unc_u8_kernel<false>, dim3(grid_for(n, kThreads, 4096)), dim3(kThreads), 0, (hipStream_t)stream,
+                       u, minmax, out, n);
   REHR_LAUNCH_CHECK();
   return REHR_OK;
 }

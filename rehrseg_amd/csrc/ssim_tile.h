@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_util.h"
 
 #pragma clang fp contract(off)
 
@@ -55,6 +56,18 @@ inline int tile_geometry(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, 
   if (g->per > INT32_MAX / N) return REHR_ENOSUP;
   g->blocks = g->per * N;
   return REHR_OK;
+}
+
+// workspace of a tile kernel: [SLOTS doubles per block: its partial sums, which the finish pass adds up per sample]
+struct TileSums {
+  double* slots;
+  int64_t bytes;
+};
+template <int SLOTS>
+inline TileSums tile_sums_layout(void* base, const Geometry& g) {
+  static_assert(SLOTS % 2 == 0, "the size is blocks * SLOTS doubles exactly: no padding to 16 bytes");
+  Carver c(base);   // a braced list is evaluated left to right
+  return {c.take<double>(g.blocks * SLOTS), c.bytes()};
 }
 
 // runs body() at the positions whose window lies inside the slice.  The test stands in an `if` of its own rather than

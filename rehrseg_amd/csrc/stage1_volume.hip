@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_util.h"
 
 #pragma clang fp contract(off)
 
@@ -75,8 +76,6 @@ __device__ __forceinline__ void bspline3_line(double* __restrict__ c, const int 
     c[i * s] = v;
   }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // lines per block: a multiple of 64 (whole waves in the recursion, 16-byte aligned regions), as many as kLdsTarget
 // holds, at least 64 (n <= kMaxN makes those fit kLdsBlock)
@@ -282,8 +281,8 @@ int launch_zoom(const float* vol, int64_t lines, int n, const int32_t* idx, cons
   if (blocks > 0x7fffffff) return REHR_ENOSUP;
   if (set_dyn_lds_once<zoom_depth_kernel<C, EVAL>>(kLdsBlock) != REHR_OK) return REHR_EHIP;
   // LB % 4 == 0: every block's regions start on a multiple of 4 elements
-  const bool vec_in = aligned16(vol);
-  const bool vec_out = aligned16(img) && (label == nullptr || (reinterpret_cast<uintptr_t>(label) & 3) == 0);
+  const bool vec_in = !misaligned(16, vol);
+  const bool vec_out = !misaligned(16, img) && !misaligned(4, label);
   hipLaunchKernelGGL((zoom_depth_kernel<C, EVAL>), dim3((unsigned)blocks), dim3(kThreads), (size_t)lds, stream, vol,
                      lines, n, idx, w, nn, Z, img, label, LB, spline3_consts(n), vec_in, vec_out);
   return REHR_OK;
@@ -297,10 +296,7 @@ extern "C" int rehr_zoom_depth_f32(const float* vol, int64_t lines, int32_t n, i
   if (vol == nullptr || idx == nullptr || w == nullptr || img == nullptr) return REHR_EINVAL;
   if (lines < 1 || n < 1 || Z < 1 || (C != 1 && C != 2)) return REHR_EINVAL;
   if (C == 2 && (nn == nullptr || label == nullptr)) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(vol) | reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(idx) |
-       reinterpret_cast<uintptr_t>(nn)) & 3)
-    return REHR_EINVAL;
-  if (reinterpret_cast<uintptr_t>(w) & 7) return REHR_EINVAL;
+  if (misaligned(4, vol, img, idx, nn) || misaligned(8, w)) return REHR_EINVAL;
   if (lines * n * C >= ((int64_t)1 << 40) || lines * Z >= ((int64_t)1 << 40)) return REHR_EINVAL;
   if (n > kMaxN) return REHR_ENOSUP;
   if ((int64_t)Z * kThreads >= ((int64_t)1 << 30)) return REHR_ENOSUP;  // a block's output run is indexed in 32 bits
@@ -317,8 +313,7 @@ extern "C" int rehr_zoom_depth_f32(const float* vol, int64_t lines, int32_t n, i
 extern "C" int rehr_bspline_prefilter_axis_f64acc_f32(const float* x, float* y, int64_t outer, int32_t n, int64_t inner,
                                                       void* stream) {
   if (x == nullptr || y == nullptr || x == y) return REHR_EINVAL;
-  if (outer < 1 || n < 1 || inner < 1) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 3) return REHR_EINVAL;
+  if (outer < 1 || n < 1 || inner < 1 || misaligned(4, x, y)) return REHR_EINVAL;
   if (outer >= ((int64_t)1 << 40) || inner >= ((int64_t)1 << 40) || outer * inner >= ((int64_t)1 << 40) ||
       outer * inner * n >= ((int64_t)1 << 40))
     return REHR_EINVAL;
@@ -346,8 +341,7 @@ extern "C" int rehr_blur_to_slices_f32(const float* img, const float* taps, int3
   if (img == nullptr || taps == nullptr || out == nullptr || img == out) return REHR_EINVAL;
   if (L < 1 || X < 1 || Y < 1 || Z < 1 || (axis != 0 && axis != 1)) return REHR_EINVAL;
   if ((int64_t)X * Y * Z >= ((int64_t)1 << 40)) return REHR_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(taps)) & 3)
-    return REHR_EINVAL;
+  if (misaligned(4, img, out, taps)) return REHR_EINVAL;
   if (L > 32) return REHR_ENOSUP;
   // a: the blurred axis, b: the other in-plane axis (the output's fastest)
   const int A = axis == 0 ? X : Y, B = axis == 0 ? Y : X;
@@ -358,7 +352,7 @@ extern "C" int rehr_blur_to_slices_f32(const float* img, const float* taps, int3
   while (chunk > 8 && (int64_t)tb * tz * ((A + chunk - 1) / chunk) < 512) chunk >>= 1;
   const dim3 grid((unsigned)tb, (unsigned)((A + chunk - 1) / chunk), (unsigned)tz);
   if (grid.y > 65535 || grid.z > 65535) return REHR_ENOSUP;
-  const bool vec = B % 4 == 0 && aligned16(out);
+  const bool vec = B % 4 == 0 && !misaligned(16, out);
 #define REHR_BLUR(LMAX)                                                                                             \
   hipLaunchKernelGGL((blur_to_slices_kernel<LMAX>), grid, dim3(kBlurThreads), 0, (hipStream_t)stream, img, taps, L, \
                      out, A, B, Z, sa, sb, chunk, vec)

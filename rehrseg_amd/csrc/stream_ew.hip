@@ -15,6 +15,7 @@
 // Column sums are kept in fp32 over a short run of rows and folded into fp64 per thread, reduced over the block
 // in LDS, and finished with one double atomic per (quantity, channel) and block: they cancel heavily.
 #include "common.h"
+#include "host_util.h"
 
 namespace {
 
@@ -496,8 +497,6 @@ __global__ __launch_bounds__(SW_THREADS) void act_bwd_kernel(const T* __restrict
   }
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // rows per block: ~2048 blocks over the whole tensor (8 per CU), at least 8 unrolled passes per block
 inline int64_t rows_per_block_for(int64_t S, int C, int N, int cpt) {
   const int rpp = SW_THREADS / (C / cpt);
@@ -521,7 +520,7 @@ int scale_res_act_fwd_t(const T* x, int ldx, const float* gate, const T* res, in
                         int C, int act, float slope, void* stream) {
   constexpr int CPT = V16<T>::N;
   if (!x || !gate || !y || !shape_ok(N, S, C, CPT) || ldx % CPT || ldy % CPT || (res && ldr % CPT)) return REHR_EINVAL;
-  if (!aligned16(x) || !aligned16(y) || (res && !aligned16(res))) return REHR_EINVAL;
+  if (misaligned(16, x, y, res)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(S, C, N, CPT);
   const dim3 grid((unsigned)((S + rpb - 1) / rpb), N);
   const float se = slope_eff_of(act, slope);
@@ -542,7 +541,7 @@ int scale_res_act_bwd_t(const T* dy, int lddy, const T* y, int ldy, const T* x, 
   constexpr int CPT = V16<T>::N;
   if (!dy || !y || !x || !gate || !dx || !dgate_acc || !shape_ok(N, S, C, CPT)) return REHR_EINVAL;
   if (lddy % CPT || ldy % CPT || ldx % CPT || lddx % CPT || (dres && lddr % CPT)) return REHR_EINVAL;
-  if (!aligned16(dy) || !aligned16(y) || !aligned16(x) || !aligned16(dx) || (dres && !aligned16(dres))) return REHR_EINVAL;
+  if (misaligned(16, dy, y, x, dx, dres)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(S, C, N, CPT);
   const dim3 grid((unsigned)((S + rpb - 1) / rpb), N);
   const float ga = slope_eff_of(act, slope);
@@ -559,7 +558,7 @@ int scale_res_act_bwd_t(const T* dy, int lddy, const T* y, int ldy, const T* x, 
 template <typename T>
 int add_channel_const_t(T* x, int ldx, const float* k, int N, int64_t S, int C, void* stream) {
   constexpr int CPT = V16<T>::N;
-  if (!x || !k || !shape_ok(N, S, C, CPT) || ldx % CPT || !aligned16(x)) return REHR_EINVAL;
+  if (!x || !k || !shape_ok(N, S, C, CPT) || ldx % CPT || misaligned(16, x)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(S, C, N, CPT);
   hipLaunchKernelGGL(add_channel_const_kernel<T>, dim3((unsigned)((S + rpb - 1) / rpb), N), dim3(SW_THREADS), 0, ST, x,
                      ldx, k, S, C, rpb);
@@ -572,7 +571,7 @@ int instnorm_act_fwd_t(const T* x, int ldx, const double* stats, const float* ga
                        float* mean_rstd, int N, int64_t S, int C, float eps, int act, float slope, void* stream) {
   constexpr int CPT = V16<T>::N;
   if (!x || !stats || !gamma || !beta || !y || !mean_rstd || !shape_ok(N, S, C, CPT)) return REHR_EINVAL;
-  if (ldx % CPT || ldy % CPT || !aligned16(x) || !aligned16(y)) return REHR_EINVAL;
+  if (ldx % CPT || ldy % CPT || misaligned(16, x, y)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(S, C, N, CPT);
   hipLaunchKernelGGL(instnorm_act_fwd_kernel<T>, dim3((unsigned)((S + rpb - 1) / rpb), N), dim3(SW_THREADS), 0, ST, x,
                      ldx, stats, gamma, beta, y, ldy, mean_rstd, S, C, rpb, 1.0 / (double)S, eps,
@@ -588,7 +587,7 @@ int instnorm_act_bwd_t(const T* dy, int lddy, const T* x, int ldx, const float* 
   constexpr int CPT = V16<T>::N;
   if (!dy || !x || !mean_rstd || !gamma || !beta || !dx || !dgamma || !dbeta || !red) return REHR_EINVAL;
   if (!shape_ok(N, S, C, CPT) || lddy % CPT || ldx % CPT || lddx % CPT) return REHR_EINVAL;
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(dx)) return REHR_EINVAL;
+  if (misaligned(16, dy, x, dx)) return REHR_EINVAL;
   const int64_t rpb = rows_per_block_for(S, C, N, CPT);
   const dim3 grid((unsigned)((S + rpb - 1) / rpb), N);
   const float ga = slope_eff_of(act, slope);
@@ -611,7 +610,7 @@ int instnorm_act_bwd_t(const T* dy, int lddy, const T* x, int ldx, const float* 
 template <typename T>
 int channel_sum_t(const T* x, int ldx, int64_t rows, int C, float* out, int accumulate, double* scratch, void* stream) {
   constexpr int CPT = V16<T>::N;
-  if (!x || !out || !scratch || !shape_ok(1, rows, C, CPT) || ldx % CPT || !aligned16(x)) return REHR_EINVAL;
+  if (!x || !out || !scratch || !shape_ok(1, rows, C, CPT) || ldx % CPT || misaligned(16, x)) return REHR_EINVAL;
   if (hipMemsetAsync(scratch, 0, sizeof(double) * C, ST) != hipSuccess) return REHR_EHIP;
   const int64_t rpb = rows_per_block_for(rows, C, 1, CPT);
   hipLaunchKernelGGL(channel_sum_kernel<T>, dim3((unsigned)((rows + rpb - 1) / rpb), 1), dim3(SW_THREADS), 0, ST, x, ldx,
@@ -624,7 +623,7 @@ int channel_sum_t(const T* x, int ldx, int64_t rows, int C, float* out, int accu
 template <typename T>
 int act_bwd_t(const T* dy, const T* y, T* dx, int64_t n, int act, float slope, void* stream) {
   constexpr int CPT = V16<T>::N;
-  if (!dy || !y || !dx || n < CPT || n % CPT || !aligned16(dy) || !aligned16(y) || !aligned16(dx)) return REHR_EINVAL;
+  if (!dy || !y || !dx || n < CPT || n % CPT || misaligned(16, dy, y, dx)) return REHR_EINVAL;
   const int64_t n16 = n / CPT;
   int64_t blocks = (n16 + SW_THREADS * SW_UNROLL - 1) / (SW_THREADS * SW_UNROLL);
   if (blocks > 4096) blocks = 4096;

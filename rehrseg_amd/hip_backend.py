@@ -98,6 +98,15 @@ def _taps(t):
     return L.AxisTaps(*t)
 
 
+def _workspace(query, args, device, what):
+    """A uint8 tensor of exactly the bytes the library's size query `query(*args)` reports; a negative answer is the
+    query's error code and raises.  Callers pass ws.numel() as the byte count."""
+    nbytes = int(query(*args))
+    if nbytes < 0:
+        L.check(nbytes, what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def _chk_dev(*ts, f64=()):
     """Every operand of the fp32 kernels must be a float32 device tensor; `f64` lists the statistics buffers
     (double accumulators) of the call."""
@@ -114,6 +123,12 @@ def _chk_dev(*ts, f64=()):
             continue
         if not t.is_cuda or t.dtype != torch.float64:
             raise L.RehrsegHipError("statistics buffers are float64 device tensors")
+
+
+def _chk_eval(t, dtype, what, dim=None):
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (dim is not None and t.dim() != dim):
+        raise L.RehrsegHipError(f"{what}: contiguous {dtype} device tensor" + (f" of {dim} dims" if dim else "") +
+                                " (no CPU fallback)")
 
 
 def _fn(base, t):
@@ -635,23 +650,17 @@ def wgrad(l, Ca, g, Cg, N, lattice, g_dims, s, b, taps, KH, KW, dst, dst_off, ds
     if bf16:
         if dbias is not None:
             raise L.RehrsegHipError("mixed-precision weight gradient has no fused bias gradient (use channel_sum)")
-        nbytes = lib.rehr_wgrad_bf16_workspace_bytes(C.byref(d))
-        if nbytes < 0:
-            L.check(int(nbytes), "rehr_wgrad_bf16_workspace_bytes")
-        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=l.device)
-        d.workspace, d.workspace_bytes = _ptr(ws), nbytes
+        ws = _workspace(lib.rehr_wgrad_bf16_workspace_bytes, (C.byref(d),), l.device, "rehr_wgrad_bf16_workspace_bytes")
+        d.workspace, d.workspace_bytes = _ptr(ws), ws.numel()
         with _timed("wgrad_bf16", flops, lambda: f"N{N} {Ca}x{Cg} lattice {tuple(lattice)} stride {tuple(s)} "
                                              f"taps {taps[0][0]}x{taps[1][0]}x{taps[2][0]}"):
             L.check(lib.rehr_wgrad_bf16(C.byref(d), _stream()), "rehr_wgrad_bf16")
         return
-    nbytes = lib.rehr_wgrad_workspace_bytes(C.byref(d))
-    if nbytes < 0:
-        L.check(int(nbytes), "rehr_wgrad_workspace_bytes")
+    ws = _workspace(lib.rehr_wgrad_workspace_bytes, (C.byref(d),), l.device, "rehr_wgrad_workspace_bytes")
     global wino_wgrad_launches
     wino = int(lib.rehr_wgrad_uses_winograd(C.byref(d)))
     wino_wgrad_launches += wino
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=l.device)
-    d.workspace, d.workspace_bytes = _ptr(ws), nbytes
+    d.workspace, d.workspace_bytes = _ptr(ws), ws.numel()
     with _timed(("wino_wgrad" if d.th.count == 3 else "wino22_wgrad") if wino else "wgrad", flops,
                 lambda: f"N{N} {Ca}x{Cg} lattice {tuple(lattice)} stride {tuple(s)} taps {taps[0][0]}x{taps[1][0]}x{taps[2][0]}"):
         L.check(lib.rehr_wgrad_f32(C.byref(d), _stream()), "rehr_wgrad_f32")
@@ -729,12 +738,12 @@ def small_cin_wgrad(x, w, dy, stride, pad, want_bias):
     if dy.dtype == torch.bfloat16 and not lib.rehr_conv_small_cin_wgrad_on_mfma(C.byref(d)):
         dy = dy.float()
         d.y = _ptr(dy)
-    nbytes = lib.rehr_conv_small_cin_wgrad_workspace_bytes(C.byref(d))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    ws = _workspace(lib.rehr_conv_small_cin_wgrad_workspace_bytes, (C.byref(d),), x.device,
+                    "rehr_conv_small_cin_wgrad_workspace_bytes")
     dw = torch.empty_like(w, memory_format=torch.contiguous_format)
     db = torch.empty(w.shape[0], dtype=torch.float32, device=x.device) if want_bias else None
     fn = lib.rehr_conv_small_cin_wgrad_dybf16 if dy.dtype == torch.bfloat16 else lib.rehr_conv_small_cin_wgrad_f32
-    L.check(fn(C.byref(d), _ptr(dw), _ptr(db), _ptr(ws), nbytes, _stream()), "rehr_conv_small_cin_wgrad")
+    L.check(fn(C.byref(d), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()), "rehr_conv_small_cin_wgrad")
     return dw, db
 
 
@@ -757,13 +766,11 @@ def small_cout_wgrad(x, w, dy, pad, want_bias):
     _chk_dev(x, w, dy)
     d = _direct_desc(x, w.contiguous(), None, dy, (1, 1, 1), pad, 0, 0.0, None, 0)
     lib = L.load()
-    nbytes = lib.rehr_conv_small_cout_wgrad_workspace_bytes(C.byref(d))
-    if nbytes < 0:
-        L.check(int(nbytes), "rehr_conv_small_cout_wgrad_workspace_bytes")
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    ws = _workspace(lib.rehr_conv_small_cout_wgrad_workspace_bytes, (C.byref(d),), x.device,
+                    "rehr_conv_small_cout_wgrad_workspace_bytes")
     dw = torch.empty_like(w, memory_format=torch.contiguous_format)
     db = torch.empty(w.shape[0], dtype=torch.float32, device=x.device) if want_bias else None
-    L.check(lib.rehr_conv_small_cout_wgrad_f32(C.byref(d), _ptr(dw), _ptr(db), _ptr(ws), nbytes, _stream()),
+    L.check(lib.rehr_conv_small_cout_wgrad_f32(C.byref(d), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
             "rehr_conv_small_cout_wgrad_f32")
     return dw, db
 
@@ -1244,18 +1251,11 @@ AUG_NOISE, AUG_SCALE, AUG_CONTRAST, AUG_CLIP, AUG_GAMMA, AUG_RETAIN = range(6)
 AUG_PW_PARAMS, AUG_STAT_PARTS = 4, 256
 
 
-def _chk_aug(x, *f64):
-    if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
-        raise L.RehrsegHipError("augmentation kernels: contiguous float32 device tensors (no CPU fallback)")
-    for t in f64:
-        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise L.RehrsegHipError("augmentation parameters / statistics: contiguous float64 device tensors")
-
-
 def aug_warp2d(src, params, out_hw, mode):
     """src (B, C, Hi, Wi) -> (B, C, Ho, Wo): the in-plane affine of every slice c of item b with params[b] (float64
     [B, AUG_WARP_PARAMS] on the device) -- rehr_aug_warp2d_f32."""
-    _chk_aug(src, params)
+    _chk_eval(src, torch.float32, "aug_warp2d src")
+    _chk_eval(params, torch.float64, "aug_warp2d params")
     B, Cc, Hi, Wi = src.shape
     Ho, Wo = (int(v) for v in out_hw)
     if params.shape != (B, AUG_WARP_PARAMS):
@@ -1268,7 +1268,9 @@ def aug_warp2d(src, params, out_hw, mode):
 
 def aug_stats(x, out=None):
     """x (B, ...) -> float64 (B, 4) {sum, sum of squares, min, max} per item (rehr_aug_stats_f32)."""
-    _chk_aug(x, out)
+    _chk_eval(x, torch.float32, "aug_stats input")
+    if out is not None:
+        _chk_eval(out, torch.float64, "aug_stats out")
     B = x.shape[0]
     S = x.numel() // B
     work = torch.empty(B * AUG_STAT_PARTS * 4, device=x.device, dtype=torch.float64)
@@ -1279,7 +1281,10 @@ def aug_stats(x, out=None):
 
 def aug_pointwise(x, op, params, stats0=None, stats1=None):
     """One intensity step in place over x (B, ...) with params float64 [B, AUG_PW_PARAMS] (rehr_aug_pointwise_f32)."""
-    _chk_aug(x, params, stats0, stats1)
+    _chk_eval(x, torch.float32, "aug_pointwise input")
+    for t in (params, stats0, stats1):
+        if t is not None:
+            _chk_eval(t, torch.float64, "aug_pointwise parameters / statistics")
     B = x.shape[0]
     if params.shape != (B, AUG_PW_PARAMS):
         raise L.RehrsegHipError("aug_pointwise: one parameter record per item")
@@ -1289,12 +1294,6 @@ def aug_pointwise(x, op, params, stats0=None, stats1=None):
 
 
 # ----------------------------------------------------------------------------- stage-2 validation (seg_eval.hip)
-def _chk_eval(t, dtype, what, dim=None):
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (dim is not None and t.dim() != dim):
-        raise L.RehrsegHipError(f"{what}: contiguous {dtype} device tensor" + (f" of {dim} dims" if dim else "") +
-                                " (no CPU fallback)")
-
-
 def tta_gather(vol, pad, start, tile, out=None):
     """vol (D, H, W) fp32, constant-padded by `pad` voxels below -> the (8, 1, d, h, w) TTA batch of the tile at
     `start` (padded coordinates): identity, then the mirrorings in itertools.combinations order (rehr_tta_gather_f32)."""
@@ -1374,10 +1373,7 @@ def seg_surface_check_extent(shape):
 
 
 def _surface_workspace(dims, device):
-    nbytes = L.load().rehr_seg_surface_workspace_bytes(*dims)
-    if nbytes < 0:
-        L.check(int(nbytes), "rehr_seg_surface_workspace_bytes")
-    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+    return _workspace(L.load().rehr_seg_surface_workspace_bytes, dims, device, "rehr_seg_surface_workspace_bytes")
 
 
 def seg_surface_distances(pred, gt, spacing, counts, workspace=None):
@@ -1435,10 +1431,7 @@ def _cc_connectivity(connectivity):
 
 def seg_cc_workspace(dims, device):
     """The workspace of seg_cc_roots / seg_cc_lesion for a (D, H, W) volume."""
-    nbytes = L.load().rehr_seg_cc_workspace_bytes(*dims)
-    if nbytes < 0:
-        L.check(int(nbytes), "rehr_seg_cc_workspace_bytes")
-    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+    return _workspace(L.load().rehr_seg_cc_workspace_bytes, dims, device, "rehr_seg_cc_workspace_bytes")
 
 
 def seg_cc_roots(mask, connectivity, workspace=None):
@@ -1512,10 +1505,7 @@ def _item_runs(x, what):
 
 def order_stats_workspace(B, R, device):
     """The workspace of order_stats for B items and R ranks."""
-    nbytes = L.load().rehr_order_stats_workspace_bytes(B, R)
-    if nbytes < 0:
-        L.check(int(nbytes), "rehr_order_stats_workspace_bytes")
-    return torch.empty(int(nbytes), device=device, dtype=torch.uint8)
+    return _workspace(L.load().rehr_order_stats_workspace_bytes, (B, R), device, "rehr_order_stats_workspace_bytes")
 
 
 def order_stats(x, ranks, out=None, workspace=None):
@@ -1773,15 +1763,12 @@ def sr_metrics(pred, target, seg_logits=None, seg_target=None, data_range=1.0):
         raise L.RehrsegHipError("sr_metrics seg_logits: the prediction's dtype")
     N, D, H, W = (int(v) for v in pred.shape)
     lib = L.load()
-    nbytes = int(lib.rehr_sr_metrics_workspace_bytes(N, D, H, W))
-    if nbytes < 0:
-        L.check(nbytes, "rehr_sr_metrics_workspace_bytes")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=pred.device)
+    ws = _workspace(lib.rehr_sr_metrics_workspace_bytes, (N, D, H, W), pred.device, "rehr_sr_metrics_workspace_bytes")
     stats = torch.empty((N, 7), dtype=torch.float64, device=pred.device)
     strides = lambda t: (C.c_int64 * 4)(*t.stride()) if t is not None else None  # noqa: E731
     fn, name = _fn("rehr_sr_metrics", pred)
     L.check(fn(_ptr(pred), strides(pred), _ptr(target), strides(target), _ptr(seg_logits), strides(seg_logits),
-               _ptr(seg_target), strides(seg_target), N, D, H, W, float(data_range), _ptr(stats), _ptr(ws), nbytes,
+               _ptr(seg_target), strides(seg_target), N, D, H, W, float(data_range), _ptr(stats), _ptr(ws), ws.numel(),
                _stream()), name)
     return stats
 
@@ -1818,16 +1805,13 @@ def structure_loss_fwd(input, target, weights, data_range=1.0, need_grad=True):
     structure_loss_bwd needs of the SSIM term, or None), all on the device; nothing is read back."""
     x, t, shape, w = _structure_loss_operands("structure_loss_fwd", input, target, weights)
     lib = L.load()
-    nbytes = int(lib.rehr_structure_loss_workspace_bytes(*shape))
-    if nbytes < 0:
-        L.check(nbytes, "rehr_structure_loss_workspace_bytes")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    ws = _workspace(lib.rehr_structure_loss_workspace_bytes, shape, x.device, "rehr_structure_loss_workspace_bytes")
     stats = torch.empty((shape[0], 4), dtype=torch.float64, device=x.device)
     loss = torch.empty((), dtype=torch.float32, device=x.device)
     fields = (torch.empty(shape[:3] + (3,) + shape[3:], dtype=torch.float32, device=x.device)
               if (need_grad and w[2] != 0.0) else None)
     L.check(lib.rehr_structure_loss_fwd_f32(_ptr(x), _strides5(x), _ptr(t), _strides5(t), *shape, *w, float(data_range),
-                                            _ptr(stats), _ptr(loss), _ptr(fields), _ptr(ws), nbytes, _stream()),
+                                            _ptr(stats), _ptr(loss), _ptr(fields), _ptr(ws), ws.numel(), _stream()),
             "rehr_structure_loss_fwd_f32")
     return loss, stats, fields
 
