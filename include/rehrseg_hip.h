@@ -797,6 +797,25 @@ int rehr_intensity_apply_f32(const float* x, float* y, int32_t B, int64_t S, int
                              int32_t mode, const double* bounds, int64_t bounds_stride, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Class locations on the device: the voxels a foreground-oversampling patch feed centres its crops on
+ * (rehrseg_amd/utils/seg_utils.py sample_class_locations drives it, csrc/class_locations.hip).
+ * label: a dense run of N uint8 voxels, 16-byte aligned, only read.  A voxel matches when label == value; value -1:
+ * when label != 0.  N <= 2^31 - 1 and R <= 2^20: REHR_ENOSUP above; a null pointer, N < 1, R < 1, a value outside
+ * [-1, 255], a misaligned pointer or too small a workspace: REHR_EINVAL; all before any launch.  Three launches,
+ * nothing read back, no atomics: the same bits on every run.
+ * ------------------------------------------------------------------------- */
+/* Bytes of the workspace of rehr_class_locations_u8 (one uint32 per chunk of 4096 voxels, rounded up to 16), or the
+ * error code. */
+int64_t rehr_class_locations_workspace_bytes(int64_t N);
+/* count[0] (int64, 8-byte aligned) = the number of matching voxels.  With rank_j = ((uint64)u[j] * count) >> 32 (u: R
+ * device words, 32-bit fractions of the count, 4-byte aligned), index[j] (int32, 4-byte aligned) = the linear index of
+ * the rank_j-th matching voxel in ascending order: numpy.flatnonzero(match)[(u.astype(uint64) * count) >> 32].  Every
+ * index[j] is -1 when count is 0.  The ranks are formed on the device, so the caller needs no count to draw them.
+ * workspace: 16-byte aligned, overwritten. */
+int rehr_class_locations_u8(const uint8_t* label, int64_t N, int32_t value, const uint32_t* u, int32_t R,
+                            int64_t* count, int32_t* index, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Stage-1 -> stage-2 volume handoff on the device (utils/sr_utils.py:137-242 inference_flavr, :279-304 zeroonenorm /
  * postprocess_flavr; rehrseg_amd/utils/sr_utils.py drives them, csrc/sr_volume.hip).
  * A "minmax" buffer is two uint32 codes {min, max} that order like the floats they stand for:

@@ -1586,6 +1586,44 @@ def intensity_apply(x, bounds, mode, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- class locations (class_locations.hip)
+CLASS_LOCATIONS_MAX_VOXELS, CLASS_LOCATIONS_MAX_RANKS = (1 << 31) - 1, 1 << 20
+
+
+def class_locations_workspace(N, device):
+    """The workspace of class_locations for a label run of N voxels."""
+    return _workspace(L.load().rehr_class_locations_workspace_bytes, (N,), device,
+                      "rehr_class_locations_workspace_bytes")
+
+
+def class_locations(label, value, u, count=None, index=None, workspace=None):
+    """label: a contiguous uint8 device tensor of any shape (16-byte aligned, not written); value: 0..255, or -1 for
+    any non-zero label; u: R 32-bit fractions as a contiguous int32 device tensor that carries the bits of numpy's
+    uint32 (torch has no arithmetic on uint32, and nothing here needs any: `torch.from_numpy(a.view(np.int32))`).
+    Returns (count int64 [1], index int32 [R]) on the device: count = the voxels that match, index[j] = the linear
+    index of the ((u[j] * count) >> 32)-th of them in ascending order, -1 everywhere when there is none
+    (rehr_class_locations_u8).  count / index: where to write them, e.g. slices of one buffer.  No host sync."""
+    _chk_eval(label, torch.uint8, "class_locations label")
+    _chk_eval(u, torch.int32, "class_locations u", 1)
+    N, R, value = label.numel(), u.numel(), int(value)
+    if not 1 <= N <= CLASS_LOCATIONS_MAX_VOXELS or not 1 <= R <= CLASS_LOCATIONS_MAX_RANKS or not -1 <= value <= 255:
+        raise L.RehrsegHipError(f"class_locations: 1..2**31 - 1 voxels, 1..2**20 fractions, a value in [-1, 255]; got "
+                                f"{N}, {R}, {value}")
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=label.device)
+    if index is None:
+        index = torch.empty(R, dtype=torch.int32, device=label.device)
+    _chk_eval(count, torch.int64, "class_locations count", 1)
+    _chk_eval(index, torch.int32, "class_locations index", 1)
+    if count.numel() != 1 or index.numel() != R:
+        raise L.RehrsegHipError("class_locations: 1 count, one index per fraction")
+    if workspace is None:
+        workspace = class_locations_workspace(N, label.device)
+    L.check(L.load().rehr_class_locations_u8(_ptr(label), N, value, _ptr(u), R, _ptr(count), _ptr(index),
+                                             _ptr(workspace), workspace.numel(), _stream()), "rehr_class_locations_u8")
+    return count, index
+
+
 # ----------------------------------------------------------------------------- stage-1 -> stage-2 handoff (sr_volume.hip)
 def minmax_new(device, pairs=1):
     """`pairs` empty {min, max} code pairs (int32 storage of the kernels' order-preserving uint32 codes)."""

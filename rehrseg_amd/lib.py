@@ -211,6 +211,8 @@ PROTOTYPES = {
     "rehr_order_stats_f32": (C.c_int, [_vp, _i32, _i64, _i64, C.POINTER(_i64), _i32, _vp, _vp, _i64, _vp]),
     "rehr_percentile_f64": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_double), _i32, _vp, _vp]),
     "rehr_intensity_apply_f32": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "rehr_class_locations_workspace_bytes": (_i64, [_i64]),
+    "rehr_class_locations_u8": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "rehr_minmax_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "rehr_sr_window_gather_f32": (C.c_int, [_vp, _vp] + [_i32] * 8 + [_vp]),
     "rehr_sr_volume_scatter_f32": (C.c_int, [_vp, _vp] + [_i32] * 7 + [_vp, _vp, _vp, _vp, _vp]),

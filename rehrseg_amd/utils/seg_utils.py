@@ -1057,3 +1057,80 @@ def evaluate_case(model, case_img, case_label, slice_separation, patch_size, get
     out = _evaluate_case(model, case_img, case_label, slice_separation, patch_size, get_HR_results, device, surface,
                          spacing, components, connectivity, norm)
     return out[:4] + out[5:]
+
+
+# ----------------------------------------------------------------------------- class locations
+def _label_u8(a, dev):
+    """A label volume as a contiguous uint8 tensor on dev: a host array is uploaded, a tensor on dev stays there."""
+    if isinstance(a, torch.Tensor):
+        t = a.detach()
+        if t.device != dev:
+            t = t.to(dev) if t.is_cuda else _upload(t.contiguous(), dev)
+        return t.to(torch.uint8).contiguous()
+    return _upload(torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8, copy=False))), dev)
+
+
+def sample_class_locations(label, classes=(1,), n=10000, seed=0, *, device=None):
+    """Voxel locations of classes of a label volume, the table a foreground-oversampling patch feed draws its crop
+    centres from: {class: int64 numpy array (m, 3)} of coordinates into `label`'s own shape, m = n for a class that
+    occurs and 0 for one that does not.
+
+    `label`: a 3-D numpy array (uploaded) or tensor (one on the device stays there; other dtypes are cast to uint8).
+    `classes`: label values 0..255, or -1 for "any non-zero label".  Row j of a class's table is the voxel of rank
+    (u[j] * count) >> 32 among the class's `count` voxels in linear (C) order, with
+    u = np.random.default_rng(seed).integers(0, 2**32, n, dtype=np.uint32), the same stream for every class; count and
+    the ranks are formed on the device (csrc/class_locations.hip), so all classes are queued before the one download
+    that is the call's only host sync.  The same label, classes, n and seed give the same table on every run.
+
+    A list (or tuple) of volumes gives a list of such dicts, volume i drawn with seed + i, still with one host sync:
+    the outputs of all volumes and classes lie in one device buffer.
+
+    Deviation from nnU-Net: its class_locations hold up to 10 000 voxels per class drawn WITHOUT replacement; this
+    table is n draws WITH replacement, uniform over the class's voxels.  A patch centre drawn uniformly from either
+    table is uniform over the class's voxels, and the with-replacement form needs no count on the host before the
+    ranks are formed."""
+    from .. import ops
+    from ..hip_backend import CLASS_LOCATIONS_MAX_RANKS, CLASS_LOCATIONS_MAX_VOXELS
+    be = ops.get_backend()
+    many = isinstance(label, (list, tuple))
+    volumes = list(label) if many else [label]
+    classes = [int(c) for c in classes]
+    n = int(n)
+    if not 1 <= n <= CLASS_LOCATIONS_MAX_RANKS:
+        raise ValueError(f"n must lie in [1, 2**20], got {n}")
+    if not classes or len(set(classes)) != len(classes) or not all(-1 <= c <= 255 for c in classes):
+        raise ValueError(f"classes: distinct label values in [0, 255], or -1 for any non-zero label; got {classes}")
+    shapes = [tuple(int(s) for s in v.shape) for v in volumes]
+    for s in shapes:
+        if len(s) != 3 or not 1 <= int(np.prod(s, dtype=np.int64)) <= CLASS_LOCATIONS_MAX_VOXELS:
+            raise ValueError(f"expected 3-D label volumes of 1 to 2**31 - 1 voxels, got {s}")
+    if not volumes:
+        return []
+    dev = _map_device(device, *volumes)
+    nv, nc = len(volumes), len(classes)
+    u = np.stack([np.random.default_rng(int(seed) + i).integers(0, 2**32, n, dtype=np.uint32) for i in range(nv)])
+    u = _upload(torch.from_numpy(u.view(np.int32)), dev)       # uint32 bits in int32 storage (hip_backend.class_locations)
+    # one buffer for everything that is read back: nv * nc counts (int64, as int32 pairs), then as many rows of n indices
+    out = torch.empty(nv * nc * (2 + n), dtype=torch.int32, device=dev)
+    counts = out[:2 * nv * nc].view(torch.int64)
+    index = out[2 * nv * nc:].view(nv * nc, n)
+    for i, v in enumerate(volumes):
+        lab = _label_u8(v, dev)
+        workspace = be.class_locations_workspace(lab.numel(), lab.device)     # one for the volume's classes
+        for k, c in enumerate(classes):
+            r = i * nc + k
+            be.class_locations(lab, c, u[i], counts[r:r + 1], index[r], workspace)
+    host = out.cpu().numpy()                                    # the one host sync
+    h_counts = host[:2 * nv * nc].view(np.int64)
+    h_index = host[2 * nv * nc:].reshape(nv * nc, n)
+    tables = []
+    for i, s in enumerate(shapes):
+        t = {}
+        for k, c in enumerate(classes):
+            r = i * nc + k
+            if h_counts[r] == 0:
+                t[c] = np.zeros((0, 3), np.int64)
+            else:
+                t[c] = np.stack(np.unravel_index(h_index[r].astype(np.int64), s), axis=1).astype(np.int64)
+        tables.append(t)
+    return tables if many else tables[0]

@@ -8,6 +8,8 @@ SAME numbers from Python's `random` in the SAME order as the reference, turns th
 operations (transpose, crop, constant pad, flip, every-k-th slice, permute) into one strided-gather descriptor per
 output (`View`, integer bookkeeping only) and launches `rehr_patch_gather` / `rehr_axis_resample_f32`
 (csrc/patch_feed.hip).  `batch(indices)` does the same for a whole batch with one launch per stage.
+Port only, off by default: the stage-2 set can centre a share of its crops on foreground voxels (nnU-Net's
+oversampling; `oversample_foreground=`) -- then, and only then, the draws differ from the reference's.
 
 What is pinned by fixtures generated from the reference's own classes (tools/gen_golden_feed.py): the random-number
 protocol, crop / pad / flip / transposition / zero-slice / permute logic of all three `__getitem__`s.  What is not
@@ -27,8 +29,8 @@ import torch
 from .. import hip_backend as hb
 from .pad import get_pads
 from .augment import DEEP_SUPERVISION_SCALES
-from .seg_utils import (_norm_spec, _normalize_on_device, get_training_transforms, zeroone_normalization,  # noqa: F401
-                        zscore_normalization)
+from .seg_utils import (_norm_spec, _normalize_on_device, get_training_transforms, sample_class_locations,  # noqa: F401
+                        zeroone_normalization, zscore_normalization)
 
 _ROTATION_FOR_DA = {"x": (-np.pi, np.pi), "y": (0, 0), "z": (0, 0)}  # utils/train_set.py:61, :260
 
@@ -313,7 +315,13 @@ class _DeviceSet(torch.utils.data.Dataset):
     def batch(self, indices):
         """The items `indices` (drawn in this order from `random`, as a loader with num_workers=0 would) stacked along a
         new leading axis, with one launch per stage instead of one per item."""
-        return self._run([self._plan(i) for i in indices])
+        return self._run(self._plan_batch(indices))
+
+    def _plan_batch(self, indices):
+        return [self._plan(i) for i in indices]
+
+    def _plan_one(self, i):
+        return self._plan(i)
 
     def __getitem__(self, i):
         if torch.utils.data.get_worker_info() is not None:
@@ -323,7 +331,7 @@ class _DeviceSet(torch.utils.data.Dataset):
                 "rehrseg_amd data sets keep their volumes in HBM and cut patches with HIP kernels: use them from the "
                 "training process (DataLoader(num_workers=0, pin_memory=False), or ds.batch(indices)), not from "
                 "DataLoader worker processes")
-        out = self._run([self._plan(i)])
+        out = self._run([self._plan_one(i)])
         return tuple(o[0] if torch.is_tensor(o) else [u[0] for u in o] if isinstance(o, list) else o for o in out)
 
 
@@ -342,11 +350,28 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
     `norm`: True (the reference's z-score) or False as before; "percentile", ("percentile", p_min, p_max) or "zeroone"
     (port only) upload a host volume raw, take a device tensor as it is, and normalise the volume once on the device
     with percentile_normalization / zeroone_normalization's kernels (no host sync); any other
-    value raises ValueError."""
+    value raises ValueError.
+    `oversample_foreground` = p in [0, 1] (port only; nnU-Net's oversample_foreground_percent, 0.33 there): 0.0
+    (default) draws every crop origin uniformly, exactly as the reference.  With p > 0 the constructor builds a table
+    of `foreground_samples` voxel locations per subject and class of `foreground_classes` on the device
+    (seg_utils.sample_class_locations with seed `foreground_seed` + subject index: draws with replacement, see its
+    docstring and DESIGN section 3.19; one host sync for the whole data set), and a FORCED item centres its crop on a
+    voxel of the table: with several classes `random.choice` among those the subject holds, then
+    table[random.randrange(len(table))], the origin clamped into the volume -- these draws stand in place of the three
+    uniform ones, the flip draws follow unchanged.  Which items are forced is nnU-Net's rule in both of its forms:
+    `__getitem__` draws one extra random.random() < p before the origin (probabilistic), `batch(indices)` forces item j
+    of B iff j >= round(B * (1 - p)) and makes no extra draw (positional).  A forced item of a subject without
+    foreground takes the uniform draws.  A p outside [0, 1] raises ValueError."""
 
     def __init__(self, image_path, split_subjects, slice_thickness, target_thickness, patch_size_ori, target_patch_size,
                  random_flip=False, uncertainty=False, preload=True, norm=True, device=None, volumes=None,
-                 train_transform=None, deep_supervision=False):
+                 train_transform=None, deep_supervision=False, *, oversample_foreground=0.0, foreground_classes=(1,),
+                 foreground_samples=10000, foreground_seed=0):
+        self.oversample_foreground = float(oversample_foreground)
+        if not 0.0 <= self.oversample_foreground <= 1.0:
+            raise ValueError(f"oversample_foreground must lie in [0, 1], got {oversample_foreground!r}")
+        self.foreground_classes = tuple(int(c) for c in foreground_classes)
+        self._locations = None
         self.image_path, self.patch_size = image_path, list(patch_size_ori)
         self.slice_thickness, self.target_thickness = slice_thickness, target_thickness
         self.separation = int(slice_thickness / target_thickness)
@@ -397,6 +422,11 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
             self.imgs.append(img if spec is None else _normalize_on_device(img, spec))
             self.labels.append(_dev(v["seg"], self.device, torch.uint8))
             self.uncertainties.append(_dev(v["uncertainty"], self.device, torch.uint8) if uncertainty else None)
+        if self.oversample_foreground > 0.0:
+            # per subject: [(class, int64 (n, 3) table)] of the classes it holds, from the labels resident in HBM
+            tables = sample_class_locations(self.labels, self.foreground_classes, foreground_samples, foreground_seed,
+                                            device=self.device)
+            self._locations = [[(c, t[c]) for c in self.foreground_classes if len(t[c])] for t in tables]
         print("Total subjects", len(self.imgs))
 
     @staticmethod
@@ -410,13 +440,31 @@ class TrainSetMultipleSegSREfficient(_DeviceSet):
     def __len__(self):
         return len(self.imgs)
 
-    def _plan(self, i):
+    def _plan_one(self, i):
+        if self._locations is None:
+            return self._plan(i)
+        return self._plan(i, random.random() < self.oversample_foreground)
+
+    def _plan_batch(self, indices):
+        if self._locations is None:
+            return [self._plan(i) for i in indices]
+        indices = list(indices)
+        first_forced = round(len(indices) * (1 - self.oversample_foreground))
+        return [self._plan(i, j >= first_forced) for j, i in enumerate(indices)]
+
+    def _plan(self, i, forced=False):
         shape = tuple(self.imgs[i].shape)
         ps, sep = self.patch_size, self.separation
         ext = (ps[0], ps[1], ps[2] * sep)
-        x0 = random.randint(0, max(shape[0] - ext[0], 0))
-        y0 = random.randint(0, max(shape[1] - ext[1], 0))
-        z0 = random.randint(0, max(shape[2] - ext[2], 0))
+        if forced and self._locations[i]:
+            present = self._locations[i]
+            table = random.choice(present)[1] if len(self.foreground_classes) > 1 else present[0][1]
+            voxel = table[random.randrange(len(table))]
+            x0, y0, z0 = (min(max(int(c) - e // 2, 0), max(s - e, 0)) for c, s, e in zip(voxel, shape, ext))
+        else:
+            x0 = random.randint(0, max(shape[0] - ext[0], 0))
+            y0 = random.randint(0, max(shape[1] - ext[1], 0))
+            z0 = random.randint(0, max(shape[2] - ext[2], 0))
         v = View(shape).crop((x0, y0, z0), ext)
         v = v.target_pad([max(s, p) for s, p in zip(v.shape, ext)])
         for axis, f in enumerate(_flips(self.random_flip)):
