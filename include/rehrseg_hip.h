@@ -508,6 +508,38 @@ int rehr_seg_loss_bwd_f32(const float* logits, int32_t ld, const float* target, 
                           float* dlogits, int32_t ldd, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Top-k cross-entropy + soft Dice (nnU-Net's DC_and_topk_loss): the CE
+ * term of the loss above replaced by the mean of the K largest elements of the loss map
+ * m that RobustCrossEntropyLoss forms before its mean: m[b][v] = ce, M = N*S elements,
+ * or with unc m[a][b][v] = ce[b][v]*unc[a][v], M = N*N*S.  Operands as
+ * rehr_seg_loss_*_f32 with N <= 4 and M <= 2^30; K is a host integer in [1, M].
+ *   fwd: one pass over the logits writes m into the workspace next to the Dice
+ *        statistics, rehr_order_stats_f32 selects t = the K-th largest element, one pass
+ *        over m counts.  stats[N*C*3 + 5] = {I,P,G per (n,c); the plain CE sum as above;
+ *        n_gt = #(m > t); n_eq = #(m == t); sum of m > t; t}.  t, n_gt and n_eq are the
+ *        same bits on every run; a NaN in m makes t NaN.  The caller forms
+ *          w_ce * (sum + (K - n_gt) * t) / K - w_dice * (the Dice mean as above).
+ *        Eleven launches and one memset, nothing read back.
+ *   bwd: one pass; an element of m carries weight 1 above t, (K - n_gt)/n_eq on t (zeros
+ *        of either sign are one value), 0 below, and
+ *          dlogits[b][v][c] = *grad_out * (w_ce/K * (sum_a weight(m[a][b][v]) * unc[a][v])
+ *                             * (softmax_c - onehot_c) + the Dice part as above).
+ *        `workspace` and `stats` are the forward's, unchanged.
+ * EINVAL: a null pointer (unc may be null), N or S < 1, K outside [1, M], ld / ldd < C,
+ * a workspace that is no multiple of 16 bytes off or smaller than the query's answer;
+ * ENOSUP: C outside 2..4, N > 4, M > 2^30.  All of them before any launch.
+ * ------------------------------------------------------------------------- */
+int64_t rehr_seg_topk_workspace_bytes(int32_t N, int32_t C, int64_t S, int32_t with_unc);
+int rehr_seg_topk_fwd_f32(const float* logits, int32_t ld, const float* target, const float* unc,
+                          int32_t N, int32_t C, int64_t S, int64_t K, double* stats, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int rehr_seg_topk_bwd_f32(const float* logits, int32_t ld, const float* target, const float* unc,
+                          int32_t N, int32_t C, int64_t S, int64_t K, const double* stats,
+                          const void* workspace, int64_t workspace_bytes, float w_ce, float w_dice,
+                          float smooth, int32_t do_bg, const float* grad_out, float* dlogits,
+                          int32_t ldd, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Deep supervision (nnU-Net's DeepSupervisionWrapper over the loss above, and
  * DownsampleSegForDSTransform2 in front of it; utils/seg_utils.py:363-371, :723-725).
  *

@@ -33,11 +33,22 @@ __device__ __forceinline__ void softmax_ce(const float* __restrict__ lp, int t, 
   ce = __logf(s) - (lt - m);
 }
 
+// A zero of either sign as +0: the top-k select orders bit patterns, the loss compares values
+__device__ __forceinline__ float plus_zero(float v) { return v == 0.f ? 0.f : v; }
+
+// weight of a selection-map element in the top-k mean: 1 above the threshold, the tie weight on it, 0 below
+__device__ __forceinline__ float topk_weight(float m, float thr, float wtie) {
+  return m > thr ? 1.f : (m == thr ? wtie : 0.f);
+}
+
 // stats[N][C][3] = {I, P, G}, stats[N*C*3] = sum_v (sum_b ce)(sum_a u); 256 threads
-template <int C>
+// MAP (seg_loss_topk.hip): the same pass also writes the per-voxel loss map the reference forms before its mean,
+// map[b][v] = ce, or with an uncertainty the broadcast product map[a][b][v] = ce[b][v] * u[a][v]
+template <int C, bool MAP = false>
 __device__ __forceinline__ void seg_loss_fwd_body(const float* __restrict__ logits, int ld,
                                                   const float* __restrict__ target, const float* __restrict__ unc,
-                                                  int N, int64_t S, double* __restrict__ stats, int bx, int nbx, int b0) {
+                                                  int N, int64_t S, double* __restrict__ stats, int bx, int nbx, int b0,
+                                                  float* __restrict__ map = nullptr) {
   float aI[SL_MAXN][C], aP[SL_MAXN][C], aG[SL_MAXN][C];
 #pragma unroll
   for (int b = 0; b < SL_MAXN; ++b)
@@ -59,6 +70,14 @@ __device__ __forceinline__ void seg_loss_fwd_body(const float* __restrict__ logi
         float p[C], ce;
         softmax_ce<C>(logits + i * ld, t, p, ce);
         sce += ce;
+        if constexpr (MAP) {
+          if (unc == nullptr) {
+            map[i] = plus_zero(ce);
+          } else {
+            for (int a = 0; a < N; ++a)
+              map[((int64_t)a * N + (b0 + b)) * S + v] = plus_zero(ce * unc[(int64_t)a * S + v]);
+          }
+        }
 #pragma unroll
         for (int c = 0; c < C; ++c) {
           const float y = (c == t) ? 1.f : 0.f;
@@ -96,12 +115,17 @@ __device__ __forceinline__ void seg_loss_fwd_body(const float* __restrict__ logi
 }
 
 // dlogits[N][S][ldd] = go * d(loss)/d(logits); 256 threads
-template <int C>
+// TOPK (seg_loss_topk.hip): the CE term is the top-k mean over the forward's map; w_ce arrives divided by K, and
+// tk = {n_gt, n_eq, sum above, threshold} of the forward, from which every block forms the tie weight
+// (K - n_gt) / n_eq.  d(loss)/d(ce[b][v]) = w_ce / K * sum_a weight(map[a][b][v]) * u[a][v].
+template <int C, bool TOPK = false>
 __device__ __forceinline__ void seg_loss_bwd_body(const float* __restrict__ logits, int ld,
                                                   const float* __restrict__ target, const float* __restrict__ unc,
                                                   int N, int64_t S, const double* __restrict__ stats, float w_ce,
                                                   float w_dice, float smooth, int do_bg, float go,
-                                                  float* __restrict__ dlogits, int ldd, int bx, int nbx, int b0) {
+                                                  float* __restrict__ dlogits, int ldd, int bx, int nbx, int b0,
+                                                  const float* __restrict__ map = nullptr,
+                                                  const double* __restrict__ tk = nullptr, double K = 0.0) {
   // per (sample, class) Dice constants: d(-dc)/dp = -(2 y den - num) / den^2 = y*A + B
   __shared__ float cA[SL_MAXN * C], cB[SL_MAXN * C];
   const int nb = (N - b0 < SL_MAXN) ? N - b0 : SL_MAXN;
@@ -120,14 +144,20 @@ __device__ __forceinline__ void seg_loss_bwd_body(const float* __restrict__ logi
     cB[threadIdx.x] = (on && raw >= 1e-8) ? (float)(k * num / (den * den)) : 0.f;
   }
   __syncthreads();
-  const float kce = w_ce / ((unc != nullptr) ? (float)((double)N * N * S) : (float)((double)N * S));
+  const float kce = TOPK ? (float)((double)w_ce / K)
+                         : w_ce / ((unc != nullptr) ? (float)((double)N * N * S) : (float)((double)N * S));
+  float thr = 0.f, wtie = 0.f;
+  if constexpr (TOPK) {
+    thr = (float)tk[3];
+    wtie = tk[1] > 0.0 ? (float)((K - tk[0]) / tk[1]) : 0.f;
+  }
   for (int64_t v = (int64_t)bx * blockDim.x + threadIdx.x; v < S; v += (int64_t)nbx * blockDim.x) {
     float su = 1.f;
-    if (unc != nullptr) {
+    if (!TOPK && unc != nullptr) {
       su = 0.f;
       for (int a = 0; a < N; ++a) su += unc[(int64_t)a * S + v];
     }
-    const float cw = kce * su;
+    float cw = kce * su;
 #pragma unroll
     for (int b = 0; b < SL_MAXN; ++b) {
       if (b < nb) {
@@ -135,6 +165,16 @@ __device__ __forceinline__ void seg_loss_bwd_body(const float* __restrict__ logi
         const int t = (int)target[i];
         float p[C], ce;
         softmax_ce<C>(logits + i * ld, t, p, ce);
+        if constexpr (TOPK) {
+          if (unc == nullptr) {
+            cw = kce * topk_weight(map[i], thr, wtie);
+          } else {
+            float acc = 0.f;
+            for (int a = 0; a < N; ++a)
+              acc += topk_weight(map[((int64_t)a * N + (b0 + b)) * S + v], thr, wtie) * unc[(int64_t)a * S + v];
+            cw = kce * acc;
+          }
+        }
         float g[C], dot = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {

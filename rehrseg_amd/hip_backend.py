@@ -1062,6 +1062,81 @@ def seg_loss_bwd(logits, target, unc, stats, w_ce, w_dice, smooth, do_bg, grad_o
     return dl
 
 
+SEG_TOPK_MAX_ELEMENTS, SEG_TOPK_MAX_SAMPLES = 1 << 30, 4
+SEG_TOPK_STATS = 4      # n_gt, n_eq, the sum above the threshold, the threshold: behind seg_loss_fwd's N*C*3 + 1
+
+
+def _ndhwc_ld(x, what):
+    """The voxel pitch of a logical (N,C,D,H,W) float32 device tensor whose memory is NDHWC: C for a dense one, more
+    for a channel slice of a wider NDHWC tensor."""
+    if x.dim() != 5 or x.dtype != torch.float32 or not x.is_cuda:
+        raise L.RehrsegHipError(f"{what}: float32 (N,C,D,H,W) device tensor (no CPU fallback)")
+    N, Cc, D, H, W = x.shape
+    ld = x.stride(4) if W > 1 else (x.stride(3) if H > 1 else (x.stride(2) if D > 1 else (x.stride(0) if N > 1 else Cc)))
+    want = (D * H * W * ld, 1, H * W * ld, W * ld, ld)
+    if ld < Cc or any(n > 1 and s != w for n, s, w in zip(x.shape, x.stride(), want)):
+        raise L.RehrsegHipError(f"{what}: NDHWC memory (ops.to_cl) or a channel slice of it, got strides {x.stride()}")
+    return ld
+
+
+def _seg_topk_operands(logits, target, unc, K):
+    ld = _ndhwc_ld(logits, "seg_topk")
+    N, Cc, D, H, W = logits.shape
+    S = D * H * W
+    for t, what in ((target, "target"), (unc, "uncertainty")):
+        if t is not None:
+            _chk_eval(t, torch.float32, f"seg_topk {what}", 2)
+            if tuple(t.shape) != (N, S):
+                raise L.RehrsegHipError(f"seg_topk: {what} is (N, S) = ({N}, {S}), got {tuple(t.shape)}")
+    M = (N * N if unc is not None else N) * S
+    if not 2 <= Cc <= 4 or N > SEG_TOPK_MAX_SAMPLES or M > SEG_TOPK_MAX_ELEMENTS:
+        raise L.RehrsegHipError("seg_topk: 2..4 classes, at most 4 samples and 2**30 loss-map elements (REHR_ENOSUP)")
+    if not 1 <= int(K) <= M:
+        raise L.RehrsegHipError(f"seg_topk: K = {K} outside [1, {M}]")
+    return ld, N, Cc, S
+
+
+def seg_topk_workspace(N, Cc, S, with_unc, device):
+    """The workspace of seg_topk_fwd / seg_topk_bwd: the loss map, the threshold and the select's own workspace."""
+    return _workspace(L.load().rehr_seg_topk_workspace_bytes, (N, Cc, S, int(bool(with_unc))), device,
+                      "rehr_seg_topk_workspace_bytes")
+
+
+def seg_topk_fwd(logits, target, unc, K, workspace=None):
+    """logits (N,C,D,H,W) NDHWC or a channel slice of it, target / unc (N,S) float32, K a Python int -> (stats double
+    [N*C*3 + 1 + 4], workspace): seg_loss_fwd's statistics, then n_gt, n_eq, the sum of the map above the threshold
+    and the threshold (rehr_seg_topk_fwd_f32).  The workspace holds the loss map for seg_topk_bwd.  No host sync."""
+    ld, N, Cc, S = _seg_topk_operands(logits, target, unc, K)
+    if workspace is None:
+        workspace = seg_topk_workspace(N, Cc, S, unc is not None, logits.device)
+    _chk_eval(workspace, torch.uint8, "seg_topk workspace", 1)
+    stats = torch.empty(N * Cc * 3 + 1 + SEG_TOPK_STATS, dtype=torch.float64, device=logits.device)
+    L.check(L.load().rehr_seg_topk_fwd_f32(_ptr(logits), ld, _ptr(target), _ptr(unc), N, Cc, S, int(K), _ptr(stats),
+                                           _ptr(workspace), workspace.numel(), _stream()), "rehr_seg_topk_fwd_f32")
+    return stats, workspace
+
+
+def seg_topk_map(workspace, N, S, with_unc):
+    """The loss map seg_topk_fwd left in its workspace: float32 (N, S), or (N, N, S) with an uncertainty (a view)."""
+    shape = (N, N, S) if with_unc else (N, S)
+    n = (N * N if with_unc else N) * S
+    return workspace[:4 * n].view(torch.float32).view(shape)
+
+
+def seg_topk_bwd(logits, target, unc, K, stats, workspace, w_ce, w_dice, smooth, do_bg, grad_out):
+    """dlogits of the loss seg_topk_fwd's statistics stand for, times grad_out (a one-element device tensor);
+    stats and workspace are the forward's (rehr_seg_topk_bwd_f32)."""
+    ld, N, Cc, S = _seg_topk_operands(logits, target, unc, K)
+    _chk_dev(grad_out, f64=(stats,))
+    _chk_eval(workspace, torch.uint8, "seg_topk workspace", 1)
+    dl = new_act(N, Cc, logits.shape[2], logits.shape[3], logits.shape[4], like=logits)
+    L.check(L.load().rehr_seg_topk_bwd_f32(_ptr(logits), ld, _ptr(target), _ptr(unc), N, Cc, S, int(K), _ptr(stats),
+                                           _ptr(workspace), workspace.numel(), float(w_ce), float(w_dice),
+                                           float(smooth), int(do_bg), _ptr(grad_out), _ptr(dl), Cc, _stream()),
+            "rehr_seg_topk_bwd_f32")
+    return dl
+
+
 def _ds_levels(logits, targets, uncs, weights, dlogits=None):
     """The host descriptors of one deep-supervision launch.  logits[l] (N,C,d,h,w) NDHWC float32, targets[l] / uncs[l]
     (N,S) float32; a level whose weight is 0 is skipped and may hold None."""

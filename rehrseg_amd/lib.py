@@ -230,6 +230,10 @@ PROTOTYPES = {
     "rehr_seg_loss_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp]),
     "rehr_seg_loss_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _f32, _f32, _f32, _i32, _vp,
                                         _vp, _i32, _vp]),
+    "rehr_seg_topk_workspace_bytes": (_i64, [_i32, _i32, _i64, _i32]),
+    "rehr_seg_topk_fwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "rehr_seg_topk_bwd_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _f32, _f32, _f32,
+                                        _i32, _vp, _vp, _i32, _vp]),
     "rehr_seg_loss_ds_fwd_f32": (C.c_int, [C.POINTER(SegDsLevel), _i32, _i32, _i32, _vp, _vp]),
     "rehr_seg_loss_ds_bwd_f32": (C.c_int, [C.POINTER(SegDsLevel), _i32, _i32, _i32, _vp, _f32, _f32, _f32, _i32, _vp,
                                            _vp]),

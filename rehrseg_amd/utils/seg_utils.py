@@ -10,6 +10,8 @@ arithmetic and is what the CPU-side tests and the oracle comparisons evaluate.  
 helpers at the end of the file mirror utils/seg_utils.py:176-287, and the validation
 after them (:45-72, :158-174, :730-784: read_image, preprocess_image, calculate_dice, evaluate_case) runs a case on
 the device through csrc/seg_eval.hip.
+`TopKLoss` / `DC_and_topk_loss` (`_build_loss(topk=k)`; not the reference's: nnU-Net's top-k CE over the same loss map,
+restated, parity unpinned) run on the device through csrc/seg_loss_topk.hip (`_FusedDCTopK`).
 `MemoryEfficientSoftDiceLoss` lives in nnunetv2==2.3.1 (absent offline): its published
 formula is restated in `SoftDiceLoss` below -- that term's parity is unpinned.
 """
@@ -209,14 +211,17 @@ class RobustCrossEntropyLoss(nn.CrossEntropyLoss):
     channel axis the loss map lacks, so (B,D,H,W) * (B,1,D,H,W) broadcasts to (B,B,D,H,W)
     before the mean -- reproduced as is."""
 
-    def forward(self, input, target, uncertainty=None):
+    def loss_map(self, input, target, uncertainty=None):
         if target.ndim == input.ndim:
             assert target.shape[1] == 1
             target = target[:, 0]
-        loss = super().forward(input, target.long())
+        loss = nn.CrossEntropyLoss.forward(self, input, target.long())
         if uncertainty is not None:
             loss = loss * uncertainty
-        return loss.mean()
+        return loss
+
+    def forward(self, input, target, uncertainty=None):
+        return self.loss_map(input, target, uncertainty).mean()
 
 
 class SoftDiceLoss(nn.Module):
@@ -311,9 +316,12 @@ class DC_and_weighted_CE_loss(nn.Module):
         no ignore label, and an uncertainty map of exactly (N,1,D,H,W) -- the shape whose product with the (N,D,H,W)
         loss map broadcasts across samples; any other uncertainty shape multiplies differently
         in the reference and takes the composition below."""
+        return net_output.is_cuda and self._fusable_config(net_output, target, uncertainty)
+
+    def _fusable_config(self, net_output, target, uncertainty):
         dc = self.dc
         N = net_output.shape[0]
-        return (net_output.is_cuda and net_output.dim() == 5 and self.ignore_label is None and
+        return (net_output.dim() == 5 and self.ignore_label is None and
                 type(dc) is SoftDiceLoss and not dc.batch_dice and dc.apply_nonlin is softmax_helper_dim1 and
                 2 <= net_output.shape[1] <= 4 and target.dim() == 5 and target.shape[1] == 1 and
                 target.numel() == net_output.numel() // net_output.shape[1] and
@@ -329,6 +337,9 @@ class DC_and_weighted_CE_loss(nn.Module):
             import warnings
             warnings.warn("DC_and_weighted_CE_loss: configuration outside the fused HIP kernel (classes > 4, ignore label, "
                           "class weights or an unusual target / uncertainty shape): composed from torch ops on the device")
+        return self._composition(net_output, target, uncertainty)
+
+    def _composition(self, net_output, target, uncertainty):
         if self.ignore_label is not None:
             assert target.shape[1] == 1
             mask = target != self.ignore_label
@@ -340,6 +351,119 @@ class DC_and_weighted_CE_loss(nn.Module):
         ce_loss = self.ce(net_output, target[:, 0], uncertainty) \
             if self.weight_ce != 0 and (self.ignore_label is None or num_fg > 0) else 0
         return self.weight_ce * ce_loss + self.weight_dice * dc_loss
+
+
+def _topk_count(M, k):
+    """K = int(M * k / 100), as TopKLoss computes it; raises before anything is launched."""
+    if not 0 < k <= 100:
+        raise ValueError(f"top-k percentage k = {k} is outside (0, 100]")
+    K = int(M * k / 100)
+    if K < 1:
+        raise ValueError(f"top-k: k = {k} % of the {M} elements of the loss map leaves none (K = {K}); "
+                         "the patch is too small for this k")
+    return K
+
+
+class TopKLoss(RobustCrossEntropyLoss):
+    """nnunetv2's TopKLoss, restated (absent offline -> parity unpinned), with RobustCrossEntropyLoss's uncertainty
+    weight: the mean of the k percent largest elements of the loss map the parent forms before its mean -- (B,D,H,W),
+    or (B,B,D,H,W) with a (B,1,D,H,W) uncertainty.  K = int(numel * k / 100)."""
+
+    def __init__(self, weight=None, ignore_index=-100, k=10, label_smoothing=0.0, **kwargs):
+        if not 0 < k <= 100:
+            raise ValueError(f"top-k percentage k = {k} is outside (0, 100]")
+        kwargs.pop("reduction", None)
+        super().__init__(weight=weight, ignore_index=ignore_index, reduction="none", label_smoothing=label_smoothing,
+                         **kwargs)
+        self.k = k
+
+    def forward(self, input, target, uncertainty=None):
+        loss = self.loss_map(input, target, uncertainty)
+        K = _topk_count(loss.numel(), self.k)
+        return loss.reshape(-1).topk(K, sorted=False)[0].mean()
+
+
+class _FusedDCTopK(torch.autograd.Function):
+    """softmax + top-k (uncertainty-weighted) CE + soft Dice on the device: the loss map, an exact select of its K-th
+    largest element and the counts around it forward, one pass backward (include/rehrseg_hip.h:
+    rehr_seg_topk_{fwd,bwd}_f32).  Elements equal to the threshold share the gradient that is
+    left: (K - n_gt) / n_eq each."""
+
+    @staticmethod
+    def forward(ctx, logits, target, unc, K, w_ce, w_dice, smooth, do_bg):
+        from .. import ops
+        be = ops.get_backend()
+        logits = ops.to_cl(logits)
+        N, C = logits.shape[:2]
+        S = logits.shape[2] * logits.shape[3] * logits.shape[4]
+        target = target.reshape(N, S).to(torch.float32).contiguous()
+        unc = None if unc is None else unc.reshape(N, S).to(torch.float32).contiguous()
+        stats, workspace = be.seg_topk_fwd(logits, target, unc, K)
+        ipg = stats[:N * C * 3].view(N, C, 3)
+        dc = (2 * ipg[..., 0] + smooth) / torch.clip(ipg[..., 2] + ipg[..., 1] + smooth, 1e-8)
+        if not do_bg:
+            dc = dc[:, 1:]
+        n_gt, _, above, thr = stats[N * C * 3 + 1:].unbind()
+        rest = K - n_gt                 # what the elements on the threshold supply; 0 * inf must not make a NaN
+        topk = (above + torch.where(rest > 0, rest * thr, torch.zeros_like(thr))) / K
+        loss = w_ce * topk - w_dice * dc.mean()
+        ctx.save_for_backward(logits, target, unc, stats, workspace)
+        ctx.cfg = (K, w_ce, w_dice, smooth, do_bg)
+        return loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .. import ops
+        logits, target, unc, stats, workspace = ctx.saved_tensors
+        K, w_ce, w_dice, smooth, do_bg = ctx.cfg
+        go = grad_out.to(torch.float32).reshape(1).contiguous()
+        dl = ops.get_backend().seg_topk_bwd(logits, target, unc, K, stats, workspace, w_ce, w_dice, smooth, do_bg, go)
+        return dl, None, None, None, None, None, None, None
+
+
+class DC_and_topk_loss(nn.Module):
+    """nnunetv2's DC_and_topk_loss, restated (absent offline -> parity unpinned) over this file's losses:
+    weight_ce * TopKLoss(k) + weight_dice * soft Dice, the Dice exactly as in DC_and_weighted_CE_loss, the CE with
+    RobustCrossEntropyLoss's optional uncertainty.  Not a DC_and_weighted_CE_loss: DeepSupervisionWrapper's one-launch
+    node must not take it, it sums this loss level by level."""
+    _warned = False
+    _fusable_config = DC_and_weighted_CE_loss._fusable_config
+    _composition = DC_and_weighted_CE_loss._composition
+
+    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None, k=10,
+                 dice_class=SoftDiceLoss):
+        super().__init__()
+        if ignore_label is not None:
+            ce_kwargs["ignore_index"] = ignore_label
+        self.weight_dice, self.weight_ce, self.ignore_label = weight_dice, weight_ce, ignore_label
+        self.ce = TopKLoss(k=k, **ce_kwargs)
+        self.dc = dice_class(apply_nonlin=softmax_helper_dim1, **soft_dice_kwargs)
+
+    def _map_elements(self, net_output, uncertainty):
+        N = net_output.shape[0]
+        return (net_output.numel() // net_output.shape[1]) * (N if uncertainty is not None else 1)
+
+    def _fusable(self, net_output, target, uncertainty):
+        """DC_and_weighted_CE_loss's conditions, at most 4 samples and a loss map the select can take."""
+        from .. import ops
+        from ..hip_backend import SEG_TOPK_MAX_ELEMENTS, SEG_TOPK_MAX_SAMPLES
+        on_device = net_output.is_cuda or getattr(ops.get_backend(), "seg_topk_on_host", False)   # the latter: tests
+        return (on_device and self._fusable_config(net_output, target, uncertainty) and
+                net_output.shape[0] <= SEG_TOPK_MAX_SAMPLES and
+                self._map_elements(net_output, uncertainty) <= SEG_TOPK_MAX_ELEMENTS)
+
+    def forward(self, net_output, target, uncertainty=None):
+        if self._fusable(net_output, target, uncertainty):
+            K = _topk_count(self._map_elements(net_output, uncertainty), self.ce.k)
+            return _FusedDCTopK.apply(net_output, target, uncertainty, K, float(self.weight_ce),
+                                      float(self.weight_dice), float(self.dc.smooth), bool(self.dc.do_bg))
+        if net_output.is_cuda and not DC_and_topk_loss._warned:
+            DC_and_topk_loss._warned = True
+            import warnings
+            warnings.warn("DC_and_topk_loss: configuration outside the fused HIP kernel (classes > 4, batch > 4, more "
+                          "than 2**30 loss-map elements, ignore label, class weights or an unusual target / uncertainty "
+                          "shape): composed from torch ops on the device")
+        return self._composition(net_output, target, uncertainty)
 
 
 @functools.lru_cache(maxsize=16)
@@ -449,12 +573,18 @@ class DeepSupervisionWrapper(nn.Module):
                    for i in live)
 
 
-def _build_loss(enable_deep_supervision=False, weight_dice=1):
+def _build_loss(enable_deep_supervision=False, weight_dice=1, topk=None):
     """ref :353-372.  With enable_deep_supervision the loss is wrapped for the network's per-stage outputs: weights
-    1 / 2**i over the reference's six scales, the last set to 0, normalised to sum 1 (:363-369)."""
-    loss = DC_and_weighted_CE_loss({"batch_dice": False, "smooth": 1e-5, "do_bg": False, "ddp": False},
-                                   {"reduction": "none"}, weight_ce=1, weight_dice=weight_dice, ignore_label=None,
-                                   dice_class=SoftDiceLoss)
+    1 / 2**i over the reference's six scales, the last set to 0, normalised to sum 1 (:363-369).
+    topk (not the reference's: nnU-Net's DC_and_topk_loss): None is the reference's loss; a
+    percentage k builds DC_and_topk_loss(k=k), whose CE term averages the hardest k % of the voxels only."""
+    dice_kwargs = {"batch_dice": False, "smooth": 1e-5, "do_bg": False, "ddp": False}
+    if topk is None:
+        loss = DC_and_weighted_CE_loss(dice_kwargs, {"reduction": "none"}, weight_ce=1, weight_dice=weight_dice,
+                                       ignore_label=None, dice_class=SoftDiceLoss)
+    else:
+        loss = DC_and_topk_loss(dice_kwargs, {}, weight_ce=1, weight_dice=weight_dice, ignore_label=None, k=topk,
+                                dice_class=SoftDiceLoss)
     if enable_deep_supervision:
         weights = np.array([1 / (2 ** i) for i in range(len(DEEP_SUPERVISION_SCALES))])
         weights[-1] = 0
